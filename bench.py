@@ -1,9 +1,13 @@
 #!/usr/bin/env python3
 """Benchmark: ES member-evals/sec (whole node) for the Sana-Sprint 1.6B one-step EGGROLL epoch.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run builds the models, runs W warmup epochs, times K epochs, writes the last timed epoch's outputs
+(--dump-outputs) and prints the headline line.  Everything else below (roofline window, per-phase and
+per-kernel tables, achievable peaks, replica check, CPU baseline, the aux record) runs only with --full.
 
 One step = one full ES epoch (noise -> perturb -> population forward of the 1.6B transformer at
 1024 px -> DC-AE decode -> CLIP-B/32 + PickScore rewards -> S all-gather -> promptnorm fitness ->
@@ -12,7 +16,7 @@ N=8 is configs[2], pop 64).  value = pop_total * K / max-over-ranks wall time of
 Synthetic data: random-init frozen weights of the Sana/DC-AE/CLIP architectures (no checkpoints
 offline), synthetic prompt embeddings, random-init LoRA.
 
-Extra fields: `roofline` of the dominant hand-written kernel (the population LoRA GEMM, MFMA-bound,
+Extra fields (--full): `roofline` of the dominant hand-written kernel (the population LoRA GEMM, MFMA-bound,
 timed live with HIP events on its launch stream during the timed epochs), `cpu_baseline` (the
 reference path restated in numpy, timed on this host's cores; rank 0, N=1 only), per-phase times.
 """
@@ -76,7 +80,15 @@ def parse():
                    help="var_d16: BASELINE configs[0] (VAR-d16, LoRA r 4, 4 classes x 4 batches) on the GPU path; "
                         "zimage: configs[3] (Z-Image-Turbo, egg rank 4, one GPU's 16 of pop 128, 384 px, 7 steps); "
                         "infinity: configs[4] (Infinity-8B 512 px, one GPU's 4 of pop 32, 10 scales, cfg 3)")
+    p.add_argument("--dump-outputs", type=str, default="", metavar="DIR",
+                   help="after the timed steps write what the last timed step returned (theta', gathered S, raw "
+                        "rewards, fitness) as DIR/<name>.npy, float32 / float64, at most 64 MB in all")
+    p.add_argument("--full", action="store_true",
+                   help="after the timed steps also run the roofline window, per-phase / per-kernel tables, achievable "
+                        "peaks, the theta replica check (N > 1) and the CPU baseline, and write the aux record")
     a = p.parse_args()
+    if a.steps < 1:
+        p.error("--steps must be at least 1")
     if a.workload == "var_d16" and a.pop_per_gpu == 8 and "--pop-per-gpu" not in sys.argv:
         a.pop_per_gpu = 4           # configs[0]: pop_size 4
     if a.workload == "zimage" and a.pop_per_gpu == 8 and "--pop-per-gpu" not in sys.argv:
@@ -360,6 +372,93 @@ def emit(full: dict, gemm: dict, args) -> None:
     print(line, flush=True)
 
 
+def emit_plain(head: dict, args) -> None:
+    """The headline line of a run without --full: the same keys, `roofline` / `cpu_baseline` null; the
+    record is written only where --aux-out names a file."""
+    aux_s = None
+    if args.aux_out:
+        try:
+            Path(args.aux_out).parent.mkdir(parents=True, exist_ok=True)
+            Path(args.aux_out).write_text(json.dumps({"line": head, "gemm": None}, indent=1, default=str))
+            aux_s = args.aux_out
+        except OSError as e:
+            log(f"aux write failed: {e}")
+    out = dict(head, roofline=None, cpu_baseline=None, details=aux_s)
+    sys.stderr.flush()
+    print(json.dumps(out, separators=(",", ":")), flush=True)
+
+
+DUMP_MAX_BYTES = 64 * 1000 * 1000
+
+
+def dump_outputs(out_dir: str, theta: torch.Tensor, stats: dict) -> None:
+    """What ESEngine.step returned in the last timed step, one DIR/<name>.npy each: theta' [D], the gathered
+    S [pop, m], the raw per-member reward means [pop, 5] and every array of the fitness record.  Floating
+    arrays are written as float32 (float64 stays), integer / bool arrays as float64.  An array over its share
+    of the 64 MB is cut to a fixed sample of its flattened elements (RandomState(0), sorted indices)."""
+    import numpy as np
+    arrays = {"theta": theta, "S": stats["_S"], "raw": stats["_raw"]}
+    arrays.update({f"fitness_{k}": v for k, v in stats["_fitness"].items() if torch.is_tensor(v)})
+    d = Path(out_dir)
+    d.mkdir(parents=True, exist_ok=True)
+    share = DUMP_MAX_BYTES // len(arrays)
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy()
+        a = a.astype(np.float64 if a.dtype.kind in "iub" or a.dtype == np.float64 else np.float32)
+        if a.nbytes > share:
+            idx = np.sort(np.random.RandomState(0).choice(a.size, share // a.itemsize, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(d / f"{name}.npy", a)
+    log(f"outputs of the last timed step written to {d} ({', '.join(arrays)})")
+
+
+def headline(args, backend, noiser, world: int, pop: int, elapsed: float) -> dict:
+    """The headline keys of the result line for the workload that ran (K timed epochs in `elapsed` s)."""
+    c = backend.cfg
+    small = "tiny-arch smoke (INVALID as metric)" if args.small else None
+    par = f"member-shard x{world} (S all-gather)"
+    if args.workload == "zimage":
+        metric = "ES member-evals/sec Z-Image-Turbo 384px egg_rank=4 (BASELINE configs[3], pop 128 over 8 GPUs)"
+        data = "synthetic (random-init Z-Image-Turbo 6B / FLUX VAE / CLIP weights, synthetic Qwen3 prompt embeds)"
+        config = {"workload": small or "zimage_turbo_384px_es_epoch",
+                  "pop_per_gpu": args.pop_per_gpu, "pop_total": pop,
+                  "images_per_member": c.prompts_per_gen * c.batches_per_gen, "resolution_px": c.width_px,
+                  "steps": c.num_inference_steps, "guidance": c.guidance_scale, "egg_rank": 4, "lora_r": c.lora_r,
+                  "lora_alpha": c.lora_alpha, "theta_D": noiser.num_params, "parallelism": par}
+    elif args.workload == "infinity":
+        metric = "ES member-evals/sec Infinity-8B 512px (BASELINE configs[4], pop 32 over 8 GPUs)"
+        data = "synthetic (random-init Infinity-8B / BSQ-VAE decoder / CLIP weights, synthetic T5 prompt features)"
+        config = {"workload": small or "infinity_8b_512px_es_epoch",
+                  "pop_per_gpu": args.pop_per_gpu, "pop_total": pop,
+                  "images_per_member": c.prompts_per_gen * c.batches_per_gen, "pn": c.pn,
+                  "scales": len(backend.es_model.scale_schedule), "cfg": c.cfg_list, "tau": c.tau_list,
+                  "top_k": c.top_k, "top_p": c.top_p, "micro_batch": c.micro_batch, "egg_rank": 1,
+                  "lora_r": c.lora_r, "lora_alpha": c.lora_alpha, "lora_targets": c.lora_target_modules,
+                  "theta_D": noiser.num_params, "parallelism": par}
+    elif args.workload == "var_d16":
+        metric = "ES member-evals/sec VAR-d16 class-conditional 256px pop=4 (BASELINE configs[0] on the GPU path)"
+        data = "synthetic (random-init VAR-d16 / VQVAE ch160 / CLIP weights; no checkpoint offline)"
+        config = {"workload": small or "var_d16_256px_es_epoch",
+                  "pop_per_gpu": args.pop_per_gpu, "pop_total": pop,
+                  "images_per_member": c.classes_per_gen * c.batches_per_gen, "classes_per_gen": c.classes_per_gen,
+                  "batches_per_gen": c.batches_per_gen, "cfg": c.guidance_scale, "top_k": c.top_k, "top_p": c.top_p,
+                  "egg_rank": 1, "lora_r": c.lora_r, "lora_alpha": c.lora_alpha, "theta_D": noiser.num_params,
+                  "parallelism": par}
+    else:
+        metric = METRIC
+        data = "synthetic (random-init Sana-Sprint-1.6B/DC-AE/CLIP-H/CLIP-B weights, synthetic prompt embeds)"
+        config = {"workload": small or "sana_sprint_1.6b_onestep_1024px_es_epoch",
+                  "pop_per_gpu": args.pop_per_gpu, "pop_total": pop, "images_per_member": 16,
+                  "prompts_per_gen": 4, "batches_per_gen": 4, "resolution_px": 32 * args.latent,
+                  "egg_rank": 1, "lora_r": 2, "lora_alpha": 8, "theta_D": noiser.num_params,
+                  "antithetic": True, "promptnorm": True, "reward": "PickScore(CLIP-H/14)+CLIP-B/32",
+                  "parallelism": par}
+    return {"metric": metric, "value": pop * args.steps / elapsed, "unit": "member-evals/s", "n_gpus": world,
+            "steps": args.steps, "warmup": args.warmup, "ms_per_step": 1e3 * elapsed / args.steps,
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "bf16", "data": data,
+            "config": config}
+
+
 def main():
     args = parse()
     rank, world, local = dist_setup(args)
@@ -371,10 +470,11 @@ def main():
     backend, engine, noiser, theta, pop = build(args, world, rank, device)
     log(f"rank {rank}: built (pop {pop}, D {noiser.num_params})")
     guidance = backend.cfg.guidance_scale
-    S_log = []   # (epoch seed, gathered S [pop, m]) per epoch: the aux record's per-epoch S digests
+    S_log = []   # (epoch seed, gathered S [pop, m]) per epoch: the aux record's per-epoch S digests (--full)
     for w in range(args.warmup):
         theta, st_w = engine.step(theta, seed=w, guidance_scale=guidance)
-        S_log.append((w, st_w.get("_S")))
+        if args.full:
+            S_log.append((w, st_w.get("_S")))
         torch.cuda.synchronize()
         log(f"rank {rank}: warmup epoch {w} done")
     torch.cuda.synchronize()
@@ -384,13 +484,24 @@ def main():
     t0 = time.perf_counter()
     for s in range(args.steps):
         theta, stats = engine.step(theta, seed=args.warmup + s, guidance_scale=guidance)
-        S_log.append((args.warmup + s, stats.get("_S")))   # host copy the step already made
+        if args.full:
+            S_log.append((args.warmup + s, stats.get("_S")))   # host copy the step already made
     torch.cuda.synchronize()
     barrier(world)
     torch.cuda.synchronize()
     elapsed = max_over_ranks(time.perf_counter() - t0, world)
     log(f"rank {rank}: timed {args.steps} epochs in {elapsed:.3f}s")
     marker()  # timed region ends
+    head = headline(args, backend, noiser, world, pop, elapsed)
+    if rank == 0 and args.dump_outputs:   # theta' and the gathered S are the same on every rank
+        dump_outputs(args.dump_outputs, theta, stats)
+    if not args.full:
+        if rank == 0:
+            emit_plain(head, args)
+        if world > 1:
+            import torch.distributed as dist
+            dist.destroy_process_group()
+        return
     # Roofline window: the same epochs again with the LoRA GEMM instrumented (HIP events on its launch
     # stream around each kernel), outside the headline timed region so the instrumentation cannot
     # touch `value`.  Its wall time is reported next to the headline one.
@@ -452,7 +563,6 @@ def main():
     if rank == 0 and not args.small:   # achievable peaks on this box next to the vendor ones
         from hyperscalees_t2i_amd.measure import achievable_peaks
         peaks = achievable_peaks(device)
-    value = pop * args.steps / elapsed
     variants = {k: v for k, v in gemm.items() if k != "all" and "tflops" in v}
     dom_name = max(variants, key=lambda k: variants[k]["total_ms"]) if variants else "all"
     dom = gemm.get(dom_name, {"launches": 0, "flops": 0.0, "avg_us": float("nan"), "tflops": float("nan")})
@@ -507,83 +617,18 @@ def main():
         from oracle import cpu_baseline
         cpu = cpu_baseline.run()
         log(f"cpu baseline: {cpu['value']:.4g} member-evals/s on {cpu['cores']} threads ({cpu.pop('wall_s'):.1f}s)")
-    if rank == 0 and args.workload == "zimage":
-        c = backend.cfg
-        line = {
-            "metric": "ES member-evals/sec Z-Image-Turbo 384px egg_rank=4 (BASELINE configs[3], pop 128 over 8 GPUs)",
-            "value": value, "unit": "member-evals/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": 1e3 * elapsed / args.steps, "higher_is_better": True, "scaling": "weak",
-            "vs_baseline": None, "dtype": "bf16",
-            "data": "synthetic (random-init Z-Image-Turbo 6B / FLUX VAE / CLIP weights, synthetic Qwen3 prompt embeds)",
-            "config": {"workload": "tiny-arch smoke (INVALID as metric)" if args.small else "zimage_turbo_384px_es_epoch",
-                       "pop_per_gpu": args.pop_per_gpu, "pop_total": pop,
-                       "images_per_member": c.prompts_per_gen * c.batches_per_gen, "resolution_px": c.width_px,
-                       "steps": c.num_inference_steps, "guidance": c.guidance_scale, "egg_rank": 4, "lora_r": c.lora_r,
-                       "lora_alpha": c.lora_alpha, "theta_D": noiser.num_params,
-                       "parallelism": f"member-shard x{world} (S all-gather)"},
-            "roofline": roofline, "cpu_baseline": None, "phases_ms": phases, "aux_kernels": aux,
-            "model_kernels": model_kernels,
-        }
-    elif rank == 0 and args.workload == "infinity":
-        c = backend.cfg
-        line = {
-            "metric": "ES member-evals/sec Infinity-8B 512px (BASELINE configs[4], pop 32 over 8 GPUs)",
-            "value": value, "unit": "member-evals/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": 1e3 * elapsed / args.steps, "higher_is_better": True, "scaling": "weak",
-            "vs_baseline": None, "dtype": "bf16",
-            "data": "synthetic (random-init Infinity-8B / BSQ-VAE decoder / CLIP weights, synthetic T5 prompt features)",
-            "config": {"workload": "tiny-arch smoke (INVALID as metric)" if args.small else "infinity_8b_512px_es_epoch",
-                       "pop_per_gpu": args.pop_per_gpu, "pop_total": pop,
-                       "images_per_member": c.prompts_per_gen * c.batches_per_gen, "pn": c.pn,
-                       "scales": len(backend.es_model.scale_schedule), "cfg": c.cfg_list, "tau": c.tau_list,
-                       "top_k": c.top_k, "top_p": c.top_p, "micro_batch": c.micro_batch, "egg_rank": 1,
-                       "lora_r": c.lora_r, "lora_alpha": c.lora_alpha, "lora_targets": c.lora_target_modules,
-                       "theta_D": noiser.num_params, "parallelism": f"member-shard x{world} (S all-gather)"},
-            "roofline": roofline, "cpu_baseline": None, "phases_ms": phases, "aux_kernels": aux,
-            "model_kernels": model_kernels,
-        }
-    elif rank == 0 and args.workload == "var_d16":
-        c = backend.cfg
-        line = {
-            "metric": "ES member-evals/sec VAR-d16 class-conditional 256px pop=4 (BASELINE configs[0] on the GPU path)",
-            "value": value, "unit": "member-evals/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": 1e3 * elapsed / args.steps, "higher_is_better": True, "scaling": "weak",
-            "vs_baseline": None, "dtype": "bf16",
-            "data": "synthetic (random-init VAR-d16 / VQVAE ch160 / CLIP weights; no checkpoint offline)",
-            "config": {"workload": "tiny-arch smoke (INVALID as metric)" if args.small else "var_d16_256px_es_epoch",
-                       "pop_per_gpu": args.pop_per_gpu, "pop_total": pop,
-                       "images_per_member": c.classes_per_gen * c.batches_per_gen, "classes_per_gen": c.classes_per_gen,
-                       "batches_per_gen": c.batches_per_gen, "cfg": c.guidance_scale, "top_k": c.top_k, "top_p": c.top_p,
-                       "egg_rank": 1, "lora_r": c.lora_r, "lora_alpha": c.lora_alpha, "theta_D": noiser.num_params,
-                       "parallelism": f"member-shard x{world} (S all-gather)"},
-            "roofline": roofline, "cpu_baseline": None, "phases_ms": phases, "aux_kernels": aux,
-            "model_kernels": model_kernels,
-        }
-    elif rank == 0:
-        line = {
-            "metric": METRIC, "value": value, "unit": "member-evals/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": 1e3 * elapsed / args.steps, "higher_is_better": True,
-            "scaling": "weak", "vs_baseline": None, "dtype": "bf16",
-            "data": "synthetic (random-init Sana-Sprint-1.6B/DC-AE/CLIP-H/CLIP-B weights, synthetic prompt embeds)",
-            "config": {"workload": ("tiny-arch smoke (INVALID as metric)" if args.small else
-                                    "sana_sprint_1.6b_onestep_1024px_es_epoch"),
-                       "pop_per_gpu": args.pop_per_gpu, "pop_total": pop, "images_per_member": 16,
-                       "prompts_per_gen": 4, "batches_per_gen": 4, "resolution_px": 32 * args.latent,
-                       "egg_rank": 1, "lora_r": 2, "lora_alpha": 8, "theta_D": noiser.num_params,
-                       "antithetic": True, "promptnorm": True, "reward": "PickScore(CLIP-H/14)+CLIP-B/32",
-                       "parallelism": f"member-shard x{world} (S all-gather)"},
-            "roofline": roofline,
+    line = dict(head, roofline=roofline, cpu_baseline=None, phases_ms=phases, aux_kernels=aux,
+                model_kernels=model_kernels)
+    if args.workload == "sana":
+        line.update({
             "cpu_baseline": cpu,
             "theta_replicas_identical": replicas_identical,
             "theta_final_sha16": theta_sha16,
             "S_epochs": S_epochs,
-            "phases_ms": phases,
-            "aux_kernels": aux,
             "aux_kernels_pop64_per_gpu": aux64,
             "aux_kernels_other_configs_per_gpu": aux_cfg,
             "aux_kernels_seeded_valu": seeded_valu_summary() if not args.small else None,
-            "model_kernels": model_kernels,
-        }
+        })
     if rank == 0:
         emit(line, gemm, args)
     if world > 1:

@@ -26,12 +26,12 @@ def test_exports_match_header():
     assert exported == set(declared)
 
 
-def test_header_compiles_as_c():
+def test_header_compiles_as_c(tmp_path):
     src = '#include "eggroll.h"\nint main(void){eggroll_mat_t m; (void)m; return (int)sizeof(eggroll_mat_t) - 48;}\n'
     r = subprocess.run(["gcc", "-x", "c", "-std=c99", "-Wall", "-Werror", f"-I{_lib.HEADER.parent}", "-", "-o",
-                        "/tmp/eggroll_hdr_test"], input=src, text=True, capture_output=True)
+                        str(tmp_path / "eggroll_hdr_test")], input=src, text=True, capture_output=True)
     assert r.returncode == 0, r.stderr
-    assert subprocess.run(["/tmp/eggroll_hdr_test"]).returncode == 0
+    assert subprocess.run([str(tmp_path / "eggroll_hdr_test")]).returncode == 0
 
 
 def test_argument_errors_are_reported():

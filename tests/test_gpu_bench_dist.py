@@ -28,7 +28,8 @@ def test_bench_two_ranks_same_device(tmp_path):
                OMP_NUM_THREADS="4")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), str(ROOT / "bench.py"),
-           "--gpus", "2", "--steps", "2", "--warmup", "1", "--small", "--no-cpu-baseline", "--pop-per-gpu", "4"]
+           "--gpus", "2", "--steps", "2", "--warmup", "1", "--small", "--full", "--no-cpu-baseline",
+           "--pop-per-gpu", "4"]
     out = tmp_path / "bench.out"
     with open(out, "w") as fo, open(tmp_path / "bench.err", "w") as fe:
         rc = subprocess.run(cmd, env=env, stdout=fo, stderr=fe, timeout=400, cwd=str(ROOT)).returncode
@@ -69,8 +70,8 @@ def test_bench_eight_ranks_configs2_partition(tmp_path):
     """BASELINE configs[2]'s partition — pop 64 as 8 ranks x 8 members — through bench.py itself
     (tiny architecture, 8 gloo ranks sharing cuda:0): every rank's theta' identical
     (verify_theta_replicas), and equal bit for bit to ONE process evaluating all 64 members."""
-    eight = _run_bench(tmp_path, "ws8", 8, ["--pop-per-gpu", "8"])
-    one = _run_bench(tmp_path, "ws1", 1, ["--pop-per-gpu", "64"])
+    eight = _run_bench(tmp_path, "ws8", 8, ["--full", "--pop-per-gpu", "8"])
+    one = _run_bench(tmp_path, "ws1", 1, ["--full", "--pop-per-gpu", "64"])
     assert eight["n_gpus"] == 8 and eight["config"]["pop_total"] == 64 and eight["config"]["pop_per_gpu"] == 8
     assert "member-shard x8" in eight["config"]["parallelism"]
     assert eight["theta_replicas_identical"] is True
@@ -92,3 +93,22 @@ def test_rccl_collectives_single_rank(tmp_path):
     res = json.loads(out.read_text())
     assert res["backend"] == "nccl" and res["world"] == 1
     assert res["gather_ok"] and res["checksum_ok"] and res["max_over_ranks"] == 3.25
+
+
+def test_bench_plain_run_dumps_outputs(tmp_path):
+    """A run without --full: the headline line alone (`roofline` / `cpu_baseline` null, no record written),
+    --steps timed epochs, and --dump-outputs leaves the last timed epoch's theta', S, raw rewards and
+    fitness record as float32 / float64 .npy files of the right shapes."""
+    import numpy as np
+    d = tmp_path / "dump"
+    line = _run_bench(tmp_path, "plain", 1, ["--pop-per-gpu", "4", "--dump-outputs", str(d)])
+    assert line["steps"] == 1 and line["warmup"] == 1 and line["n_gpus"] == 1 and line["dtype"] == "bf16"
+    assert line["value"] > 0 and line["unit"] == "member-evals/s" and line["higher_is_better"] is True
+    assert abs(line["ms_per_step"] * line["value"] - 1e3 * 4) < 1e-6 * 4e3     # pop 4, one timed step
+    assert line["roofline"] is None and line["cpu_baseline"] is None and line["details"] is None
+    got = {p.stem: np.load(p) for p in d.glob("*.npy")}
+    assert {"theta", "S", "raw"} <= set(got) and any(k.startswith("fitness_") for k in got)
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    assert got["theta"].shape == (line["config"]["theta_D"],) and got["S"].shape[0] == 4 and got["raw"].shape == (4, 5)
+    assert np.isfinite(got["theta"]).all() and np.isfinite(got["S"]).all() and np.abs(got["theta"]).max() > 0
+    assert sum(p.stat().st_size for p in d.glob("*.npy")) <= 64 * 1000 * 1000 + 128 * len(got)

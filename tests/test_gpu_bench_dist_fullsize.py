@@ -40,7 +40,8 @@ def _run(tmp_path, tag, nproc, extra):
                "--gpus", str(nproc)]
     else:
         cmd = [sys.executable, str(ROOT / "bench.py")]
-    cmd += ["--steps", "1", "--warmup", "1", "--no-cpu-baseline", "--aux-out", str(tmp_path / f"{tag}_aux.json")] + extra
+    cmd += ["--steps", "1", "--warmup", "1", "--full", "--no-cpu-baseline",
+            "--aux-out", str(tmp_path / f"{tag}_aux.json")] + extra
     out, err = tmp_path / f"{tag}.out", tmp_path / f"{tag}.err"
     with open(out, "w") as fo, open(err, "w") as fe:
         rc = subprocess.run(cmd, env=env, stdout=fo, stderr=fe, timeout=1500, cwd=str(ROOT)).returncode

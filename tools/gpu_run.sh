@@ -30,6 +30,7 @@ for st in "$@"; do
     bench)
       say bench
       timeout -k 10 900 python -u bench.py --steps 10 --warmup 3 --aux-out gpurun_out/${tag}_bench_aux.json \
+          --full \
           > gpurun_out/${tag}_bench.json 2> gpurun_out/${tag}_bench.err || { tail -30 gpurun_out/${tag}_bench.err; exit 1; }
       cut -c1-600 gpurun_out/${tag}_bench.json ;;
     prof)
