@@ -90,6 +90,8 @@ SIGNATURES = {
                                              i64, i32, vp]),
     "eggroll_clip_preprocess": (C.c_int, [vp, i64, i64, i64, i64, i64, i64, i64, i32, vp, vp, i32, i32, i64, i64,
                                           i64, vp, vp, vp, vp, vp]),
+    "eggroll_relbias_attention": (C.c_int, [vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, i64, i64, i64, f32, vp, i64,
+                                            vp]),
 }
 
 _lib = None

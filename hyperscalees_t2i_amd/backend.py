@@ -659,15 +659,26 @@ class InfinityBackend(ESBackend):
         self.image_pil_mode = 2          # rewards: Infinity's bf16 (x + 1) / 2 * 255 -> uint8
 
     def _load_or_encode_prompts(self):
-        """es_backend.py:749-801 (no T5 offline: an encoded file, or the synthetic set when no path is set)."""
+        """es_backend.py:749-801: an encoded file; with auto_encode_if_missing, that file encoded from
+        prompts_txt_path by the T5 of the local directory text_encoder_ckpt (built on its own: no temporary
+        Infinity model); or the synthetic set when no path is set."""
         c = self.cfg
         if c.encoded_prompt_path:
             enc = Path(c.encoded_prompt_path)
             if not enc.is_file():
                 if not c.auto_encode_if_missing:
                     raise FileNotFoundError(f"encoded_prompt_path not found and auto_encode disabled: {enc}")
-                raise FileNotFoundError(f"encoded_prompt_path not found and the T5 encoder is not available "
-                                        f"offline: {enc}")
+                txt = Path(c.prompts_txt_path)
+                if not txt.is_file():
+                    raise FileNotFoundError(f"prompts_txt_path not found: {txt}")
+                from .infinity_pipeline import T5PromptEncoder
+                pe = T5PromptEncoder(c.text_encoder_ckpt, self.device,
+                                     c.arch.text_channels if c.arch is not None else c.text_channels)
+                pe.encode_file(txt, enc, batch_size=int(c.encode_batch_size), store_dtype="float16",
+                               enable_positive_prompt=int(c.enable_positive_prompt))
+                if c.drop_text_encoder_after_encode:
+                    pe.drop()
+                del pe
             self.prompt_data = torch.load(enc, map_location="cpu", weights_only=True)
         else:
             a = c.arch

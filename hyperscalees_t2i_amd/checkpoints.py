@@ -630,3 +630,90 @@ def save_infinity_checkpoint(model, vae, model_path: Path, vae_path: Path, shard
     vp = Path(vae_path)
     vp.parent.mkdir(parents=True, exist_ok=True)
     torch.save({k: v.detach().cpu().contiguous() for k, v in state_from_build(vae, bsq_vae_rules(vae)).items()}, str(vp))
+
+
+# ---------------------------------------------------------------------------------------
+# T5 encoder (the flan-t5-xl prompt encoder of the Infinity host, models/Infinity.py:121-129): a local
+# Hugging Face directory, config.json + model.safetensors (or the sharded form with its index, which is
+# how flan-t5-xl ships), transformers' key names.  The decoder, the LM head and the duplicate
+# encoder.embed_tokens.weight of the full seq2seq checkpoint are ignored by prefix; strict otherwise.
+# ---------------------------------------------------------------------------------------
+T5_WEIGHTS_NAME = "model.safetensors"
+T5_WEIGHTS_INDEX = "model.safetensors.index.json"
+T5_IGNORE = ("decoder.", "lm_head.weight", "encoder.embed_tokens.weight")
+
+
+def t5_arch_from_config(cfg: dict):
+    from .t5 import T5Arch
+    if int(cfg.get("d_kv", 64)) != 64:
+        raise NotImplementedError(f"T5 d_kv={cfg.get('d_kv')} (the attention kernel is head dim 64 only)")
+    ffp = cfg.get("feed_forward_proj", "relu")
+    if ffp != "gated-gelu":
+        raise NotImplementedError(f"T5 feed_forward_proj={ffp!r} (only gated-gelu, flan-t5's, is built)")
+    return T5Arch(d_model=int(cfg["d_model"]), d_kv=64, num_heads=int(cfg["num_heads"]), d_ff=int(cfg["d_ff"]),
+                  num_layers=int(cfg["num_layers"]), num_buckets=int(cfg.get("relative_attention_num_buckets", 32)),
+                  max_distance=int(cfg.get("relative_attention_max_distance", 128)),
+                  eps=float(cfg.get("layer_norm_epsilon", 1e-6)), vocab_size=int(cfg["vocab_size"]))
+
+
+def t5_config_from_arch(a) -> dict:
+    return {"model_type": "t5", "architectures": ["T5EncoderModel"], "d_model": a.d_model, "d_kv": a.d_kv,
+            "num_heads": a.num_heads, "d_ff": a.d_ff, "num_layers": a.num_layers,
+            "relative_attention_num_buckets": a.num_buckets, "relative_attention_max_distance": a.max_distance,
+            "layer_norm_epsilon": a.eps, "vocab_size": a.vocab_size, "feed_forward_proj": "gated-gelu"}
+
+
+def t5_rules(model: nn.Module) -> List[Rule]:
+    rules = [_same("embed", "shared.weight"),
+             _same("rel_bias", "encoder.block.0.layer.0.SelfAttention.relative_attention_bias.weight"),
+             _same("final_ln", "encoder.final_layer_norm.weight")]
+    for i in range(len(model.blocks)):
+        b, e = f"blocks.{i}", f"encoder.block.{i}.layer"
+        rules += [(f"{b}.wqkv", [f"{e}.0.SelfAttention.{n}.weight" for n in "qkv"], lambda ts: torch.cat(ts, 0),
+                   lambda t: list(t.chunk(3, 0))),
+                  _same(f"{b}.wo", f"{e}.0.SelfAttention.o.weight"), _same(f"{b}.ln1", f"{e}.0.layer_norm.weight"),
+                  _same(f"{b}.wi0", f"{e}.1.DenseReluDense.wi_0.weight"),
+                  _same(f"{b}.wi1", f"{e}.1.DenseReluDense.wi_1.weight"),
+                  _same(f"{b}.wo_ff", f"{e}.1.DenseReluDense.wo.weight"), _same(f"{b}.ln2", f"{e}.1.layer_norm.weight")]
+    return rules
+
+
+def read_t5_state(d: Path) -> Dict[str, torch.Tensor]:
+    from safetensors.torch import load_file
+    d = Path(d)
+    if (d / T5_WEIGHTS_NAME).is_file():
+        return load_file(str(d / T5_WEIGHTS_NAME))
+    if (d / T5_WEIGHTS_INDEX).is_file():
+        index = json.loads((d / T5_WEIGHTS_INDEX).read_text())
+        out: Dict[str, torch.Tensor] = {}
+        for shard in sorted(set(index["weight_map"].values())):
+            out.update(load_file(str(d / shard)))
+        missing = set(index["weight_map"]) - set(out)
+        if missing:
+            raise ValueError(f"{d}: index names tensors absent from its shards: {sorted(missing)[:3]}")
+        return out
+    if list(d.glob("pytorch_model*.bin")):
+        raise FileNotFoundError(f"{d}: only pytorch_model*.bin found; .bin / pickle T5 checkpoints are not "
+                                f"supported, convert to {T5_WEIGHTS_NAME}")
+    raise FileNotFoundError(f"{d}: no {T5_WEIGHTS_NAME} (or {T5_WEIGHTS_INDEX}) found")
+
+
+def load_t5_encoder(d: Path, device="cpu"):
+    """T5Encoder from a local Hugging Face directory (a T5EncoderModel's or the full seq2seq model's)."""
+    from .t5 import T5Encoder
+    d = Path(d)
+    if not d.is_dir():
+        raise FileNotFoundError(f"{d}: not a local T5 checkpoint directory")
+    enc = T5Encoder(t5_arch_from_config(read_config(d))).to(device)
+    load_into(enc, t5_rules(enc), read_t5_state(d), f"{d} (T5 encoder)", ignore_prefixes=T5_IGNORE)
+    return enc
+
+
+def save_t5_encoder(enc, d: Path) -> None:
+    """The build's T5 encoder weights in transformers' T5EncoderModel layout (round trips, tools)."""
+    from safetensors.torch import save_file
+    d = Path(d)
+    d.mkdir(parents=True, exist_ok=True)
+    st = state_from_build(enc, t5_rules(enc))
+    save_file({k: v.detach().cpu().contiguous() for k, v in st.items()}, str(d / T5_WEIGHTS_NAME))
+    (d / "config.json").write_text(json.dumps(t5_config_from_arch(enc.arch), indent=2))

@@ -2624,6 +2624,199 @@ extern "C" int eggroll_flash_attention(const void* q, int64_t q_bs, int64_t ldq,
 }
 
 // ------------------------------------------------------------------------------------
+// Attention with a relative-position bias and per-sequence key lengths, head dim 64 (the T5 encoder):
+//   o[b, i, h, :] = softmax_{j < len[b]}(scale * q[b,i,h,:] . k[b,j,h,:] + rel_bias[h][j - i + R-1]) @ v[b, j, h, :]
+// q / k / v / o: rows b*N + i of bf16 matrices with their own row strides, head h at columns 64 h (the
+// [B*N, 3*heads*64] output of one fused qkv GEMM is read in place).  k_flash_attn's scheme at head dim 64:
+// workgroup = (b, h, 64-query block), 4 waves x 16 queries, keys in blocks of 64 staged in LDS (the next
+// block held in registers), S^T = K Q^T so each lane holds 4 keys of ONE query and the bias index
+// key - query is one subtraction per score.  The head's bias row sits in LDS as sb[d + 511], d = key - query
+// (pre-multiplied by log2 e; zero where |d| >= N, which only padded queries / masked keys reach), so the
+// index needs no clamp for any key / query of a 64-padded N <= 512.  Only the blocks holding keys < len[b]
+// are swept, keys >= len[b] inside the last one take -inf, and key rows are read clamped to len[b] - 1:
+// nothing past row N - 1 of a sequence is touched.  Query rows >= len[b] are written as zeros.
+// ------------------------------------------------------------------------------------
+constexpr int RB_HD = 64, RB_KB = 64, RB_QB = 64, RB_RS = RB_HD + 8, RB_NMAX = 512;
+
+__global__ __launch_bounds__(256) void k_relbias_attn(const unsigned short* __restrict__ q, int64_t ldq,
+                                                      const unsigned short* __restrict__ k, int64_t ldk,
+                                                      const unsigned short* __restrict__ v, int64_t ldv,
+                                                      const float* __restrict__ rel_bias, int R,
+                                                      const int* __restrict__ lens, int heads, int N, int nqb,
+                                                      float scale_log2, unsigned short* __restrict__ o, int64_t ldo) {
+    constexpr int KSN = RB_HD / 32, DF = RB_HD / 16, KF = RB_KB / 16, CH = RB_HD / 8;
+    constexpr int UNITS = 2 * RB_KB * CH / 256;   // 16-B chunks of k + v per thread per key block (4)
+    __shared__ __attribute__((aligned(16))) unsigned short sk[RB_KB * RB_RS];
+    __shared__ __attribute__((aligned(16))) unsigned short sv[RB_KB * RB_RS];
+    __shared__ float sb[2 * RB_NMAX];
+    const int bid = xcd_remap(blockIdx.x, gridDim.x);
+    const int qb = bid % nqb, bh = bid / nqb;
+    const int b = bh / heads, h = bh - b * heads;
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, r16 = lane & 15, g = lane >> 4;
+    const int L = min(max(lens[b], 0), N);
+    const int64_t row0 = (int64_t)b * N;
+    if (qb * RB_QB >= L) {   // no valid query in this block (block-uniform): zeros, before any barrier
+#pragma unroll
+        for (int i = 0; i < RB_QB * (RB_HD / 4) / 256; ++i) {
+            const int c = tid + 256 * i, r = c / (RB_HD / 4), cc = c - r * (RB_HD / 4);
+            if (qb * RB_QB + r < N)
+                *reinterpret_cast<u16x4m*>(o + (row0 + qb * RB_QB + r) * ldo + (int64_t)h * RB_HD + 4 * cc) =
+                    u16x4m{0, 0, 0, 0};
+        }
+        return;
+    }
+    for (int t = tid; t < 2 * RB_NMAX; t += 256) {
+        const int d = t - (RB_NMAX - 1);
+        sb[t] = (d > -N && d < N) ? rel_bias[(int64_t)h * (2 * R - 1) + d + (R - 1)] * 1.4426950408889634f : 0.0f;
+    }
+    const unsigned short* kb_ = k + row0 * ldk + (int64_t)h * RB_HD;
+    const unsigned short* vb_ = v + row0 * ldv + (int64_t)h * RB_HD;
+    // Q^T fragments (B operand): dims 32 ks + 8 g .. +7 of query r16 of this wave's 16
+    const int qr = qb * RB_QB + w * 16 + r16;
+    la_bf16x8 bq[KSN];
+#pragma unroll
+    for (int ks = 0; ks < KSN; ++ks) {
+        u16x8m t = u16x8m{0, 0, 0, 0, 0, 0, 0, 0};
+        if (qr < N) t = *reinterpret_cast<const u16x8m*>(q + (row0 + qr) * ldq + (int64_t)h * RB_HD + 32 * ks + 8 * g);
+        bq[ks] = __builtin_bit_cast(la_bf16x8, t);
+    }
+    u16x8m pre[UNITS];
+    auto load_blk = [&](int key0) {
+#pragma unroll
+        for (int i = 0; i < UNITS; ++i) {
+            const int c = tid + 256 * i;             // [k | v][row][chunk]
+            const int kv = c / (RB_KB * CH), rc = c - kv * (RB_KB * CH);
+            const int r = rc / CH, cc = rc - r * CH;
+            // branch-free: rows past L read the last valid key (in bounds) and are zeroed by a select
+            const int row = min(key0 + r, L - 1);
+            const unsigned short* src = kv ? vb_ + (int64_t)row * ldv : kb_ + (int64_t)row * ldk;
+            const u16x8m t = *reinterpret_cast<const u16x8m*>(src + cc * 8);
+            pre[i] = key0 + r < L ? t : u16x8m{0, 0, 0, 0, 0, 0, 0, 0};
+        }
+    };
+    auto store_blk = [&]() {
+#pragma unroll
+        for (int i = 0; i < UNITS; ++i) {
+            const int c = tid + 256 * i;
+            const int kv = c / (RB_KB * CH), rc = c - kv * (RB_KB * CH);
+            const int r = rc / CH, cc = rc - r * CH;
+            *reinterpret_cast<u16x8m*>((kv ? sv : sk) + r * RB_RS + cc * 8) = pre[i];
+        }
+    };
+    la_f32x4 oc[DF];
+#pragma unroll
+    for (int d = 0; d < DF; ++d) oc[d] = la_f32x4{0.f, 0.f, 0.f, 0.f};
+    float m = -INFINITY, l = 0.0f;
+    const int nkb = (L + RB_KB - 1) / RB_KB;
+    load_blk(0);
+    for (int kb = 0; kb < nkb; ++kb) {
+        __syncthreads();   // every wave is done reading the previous block (first trip: sb is being written)
+        store_blk();
+        __syncthreads();
+        if (kb + 1 < nkb) load_blk((kb + 1) * RB_KB);   // in flight under this block's MFMAs
+        la_f32x4 sf[KF];
+#pragma unroll
+        for (int ks = 0; ks < KSN; ++ks) {
+#pragma unroll
+            for (int f = 0; f < KF; ++f) {
+                const la_bf16x8 a = *reinterpret_cast<const la_bf16x8*>(sk + (16 * f + r16) * RB_RS + 32 * ks + 8 * g);
+                sf[f] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, bq[ks], ks ? sf[f] : la_f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
+            }
+        }
+        const int key0 = kb * RB_KB;
+        // t = log2 e * (scale * s + bias[key - query]); lane: keys key0 + 16 f + 4 g + e of query qr.
+        // key <= 511 and qr <= 511 (64-padded N <= 512), so the index lies in [0, 1022]
+        const float* bl = sb + (key0 + 4 * g - qr + (RB_NMAX - 1));
+#pragma unroll
+        for (int f = 0; f < KF; ++f)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) sf[f][e] = fmaf(sf[f][e], scale_log2, bl[16 * f + e]);
+        if (key0 + RB_KB > L) {   // the partial last block: keys >= L -> -inf (uniform branch)
+#pragma unroll
+            for (int f = 0; f < KF; ++f)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) sf[f][e] = key0 + 16 * f + 4 * g + e < L ? sf[f][e] : -INFINITY;
+        }
+        float mb = fmaxf(fmaxf(sf[0][0], sf[0][1]), fmaxf(sf[0][2], sf[0][3]));
+#pragma unroll
+        for (int f = 1; f < KF; ++f) mb = fmaxf(fmaxf(mb, fmaxf(sf[f][0], sf[f][1])), fmaxf(sf[f][2], sf[f][3]));
+        mb = g4_max(mb);   // finite: key key0 of every swept block is < L
+        const float mn = fmaxf(m, mb);
+        if (__builtin_amdgcn_ballot_w64(mn != m)) {   // a running max moved: rescale
+            const float alpha = __builtin_amdgcn_exp2f(m - mn);   // 0 on the first block (m = -inf)
+            l *= alpha;
+#pragma unroll
+            for (int d = 0; d < DF; ++d)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) oc[d][e] *= alpha;
+            m = mn;
+        }
+        float acc = 0.f;
+#pragma unroll
+        for (int f = 0; f < KF; ++f)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                sf[f][e] = __builtin_amdgcn_exp2f(sf[f][e] - mn);
+                acc += sf[f][e];
+            }
+        l += acc;
+#pragma unroll
+        for (int j = 0; j < KF / 2; ++j) {
+            la_bf16x8 bp;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                bp[e] = (__bf16)sf[2 * j][e];
+                bp[4 + e] = (__bf16)sf[2 * j + 1][e];
+            }
+#pragma unroll
+            for (int d = 0; d < DF; ++d) {
+                const la_bf16x8 av = xa_tr8_perm<RB_RS>(sv + (32 * j) * RB_RS + 16 * d, lane);
+                oc[d] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av, bp, oc[d], 0, 0, 0);
+            }
+        }
+    }
+    const float sum = g4_sum(l);
+    if (qr < N) {
+        const bool valid = qr < L;
+        const float inv = 1.0f / sum;
+        unsigned short* dst = o + (row0 + qr) * ldo + (int64_t)h * RB_HD + 4 * g;
+#pragma unroll
+        for (int d = 0; d < DF; ++d) {
+            u16x4m t;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) t[e] = valid ? f2b(oc[d][e] * inv) : (unsigned short)0;
+            *reinterpret_cast<u16x4m*>(dst + 16 * d) = t;
+        }
+    }
+}
+
+extern "C" int eggroll_relbias_attention(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v,
+                                         int64_t ldv, const float* rel_bias, int64_t R, const int32_t* lens, int64_t B,
+                                         int64_t heads, int64_t N, int64_t head_dim, float scale, void* o, int64_t ldo,
+                                         void* stream) {
+    EGG_CHECK_ARG(head_dim == RB_HD, "relbias_attention: head_dim %lld unsupported (64)", (long long)head_dim);
+    EGG_CHECK_ARG(B >= 0 && heads >= 1, "relbias_attention: bad sizes B=%lld heads=%lld", (long long)B, (long long)heads);
+    if (B == 0) return EGGROLL_OK;
+    EGG_CHECK_ARG(N >= 1 && N <= RB_NMAX, "relbias_attention: N=%lld outside [1, %d]", (long long)N, RB_NMAX);
+    EGG_CHECK_ARG(R >= N && R < (1ll << 24), "relbias_attention: rel_bias is [heads][2R-1] with R >= N (R=%lld, N=%lld)",
+                  (long long)R, (long long)N);
+    EGG_CHECK_ARG(ldq % 8 == 0 && ldk % 8 == 0 && ldv % 8 == 0 && ldo % 4 == 0 && ldq >= heads * RB_HD &&
+                  ldk >= heads * RB_HD && ldv >= heads * RB_HD && ldo >= heads * RB_HD, "relbias_attention: bad strides");
+    EGG_CHECK_ARG(q && k && v && o && rel_bias && lens, "relbias_attention: NULL pointer");
+    EGG_CHECK_ARG(((uintptr_t)q & 15) == 0 && ((uintptr_t)k & 15) == 0 && ((uintptr_t)v & 15) == 0 && ((uintptr_t)o & 7) == 0 &&
+                  ((uintptr_t)rel_bias & 3) == 0 && ((uintptr_t)lens & 3) == 0,
+                  "relbias_attention: q/k/v must be 16-byte aligned, o 8-byte aligned");
+    const int64_t nqb = (N + RB_QB - 1) / RB_QB;
+    EGG_CHECK_ARG(B * heads * nqb < (1ll << 31), "relbias_attention: grid too large");
+    hipLaunchKernelGGL(k_relbias_attn, dim3((unsigned)(B * heads * nqb)), dim3(256), 0, as_stream(stream),
+                       (const unsigned short*)q, ldq, (const unsigned short*)k, ldk, (const unsigned short*)v, ldv,
+                       rel_bias, (int)R, lens, (int)heads, (int)N, (int)nqb, scale * 1.4426950408889634f,
+                       (unsigned short*)o, ldo);
+    EGG_CHECK_LAUNCH("relbias_attention");
+    return EGGROLL_OK;
+}
+
+// ------------------------------------------------------------------------------------
 // GroupNorm (+ SiLU) on NHWC bf16 activations (the FLUX / Infinity VAE decoders' GroupNorm(32)):
 //   y[b, p, c] = act((x - mean[b, g]) * rstd[b, g] * w[c] + bias[c]),  g = c / (C / G),
 // statistics over the H*W pixels and C/G channels of (b, g), biased variance, fp32 data path.

@@ -5,8 +5,9 @@ Reference semantics kept: prompts arrive as per-prompt "compact" T5 features [L_
 lengths (models/Infinity.py:257-335, 362-388); one call generates all images of a list with per-scale
 cfg / tau lists (a scalar repeats, a short list pads with its last value, a long one truncates:
 models/Infinity.py:463-489); every call seeds its sampling generator with `seed`; images come back
-as PIL after Infinity's `(img + 1) / 2 * 255 -> uint8` and the channel flip.  The text encoder
-(flan-t5-xl) is not available offline: prompts come from an encoded file or the synthetic set.
+as PIL after Infinity's `(img + 1) / 2 * 255 -> uint8` and the channel flip.  Prompts come from an
+encoded file, the synthetic set, or a prompt .txt encoded by the T5 encoder (t5.py) of a local
+Hugging Face directory (T5PromptEncoder; there is no hub access).
 Knobs the reference passes through to Infinity that change sampling beyond top-k / top-p (gumbel,
 cfg_exp_k, softmax_merge_topk, gt_leak, sampling_per_bits > 1, negative prompts, a non-zero
 cfg_insertion_layer) raise NotImplementedError instead of being ignored.
@@ -58,6 +59,83 @@ def to_pil_infinity(images: torch.Tensor) -> List[Any]:
     return [Image.fromarray(a) for a in arr]
 
 
+def load_prompts_from_txt(path) -> List[str]:
+    """models/Infinity.py:240-243: one prompt per line; blank lines and # lines are skipped."""
+    lines = Path(path).read_text(encoding="utf-8").splitlines()
+    return [ln.strip() for ln in lines if ln.strip() and not ln.strip().startswith("#")]
+
+
+_PERSON_KEYS = ("man", "woman", "men", "women", "boy", "girl", "child", "person", "human", "adult", "teenager",
+                "employee", "employer", "worker", "mother", "father", "sister", "brother", "grandmother",
+                "grandfather", "son", "daughter")
+
+
+def aug_with_positive_prompt(prompt: str) -> str:
+    """models/Infinity.py:245-255 (substring match, as there)."""
+    if any(key in prompt for key in _PERSON_KEYS):
+        prompt = prompt + ". very smooth faces, good looking faces, face to the camera, perfect facial features"
+    return prompt
+
+
+class T5PromptEncoder:
+    """The text side of InfinityES on its own (models/Infinity.py:121-129, 257-335): the tokenizer and the T5
+    encoder of a local Hugging Face directory.  Building it never instantiates the Infinity transformer."""
+
+    MAX_LENGTH = 512
+
+    def __init__(self, text_encoder_ckpt, device: str, text_channels: int):
+        d = Path(str(text_encoder_ckpt))
+        if not d.is_dir():
+            raise FileNotFoundError(f"text_encoder_ckpt {text_encoder_ckpt}: not a local directory (config.json, "
+                                    "model.safetensors and the tokenizer files of a T5 checkpoint; there is no hub "
+                                    "access)")
+        from . import checkpoints as ck
+        arch = ck.t5_arch_from_config(ck.read_config(d))
+        if arch.d_model != int(text_channels):
+            raise ValueError(f"{d}: T5 d_model {arch.d_model} != text_channels {int(text_channels)}")
+        from transformers import AutoTokenizer
+        self.tokenizer = AutoTokenizer.from_pretrained(str(d), legacy=True)
+        self.tokenizer.model_max_length = self.MAX_LENGTH
+        self.device = device
+        self.encoder = ck.load_t5_encoder(d, device)
+
+    def tokenize(self, prompts: Sequence[str]) -> Tuple[torch.Tensor, torch.Tensor]:
+        """(input_ids [B, 512], lens [B]) as models/Infinity.py:302-316."""
+        tok = self.tokenizer(text=list(prompts), max_length=self.MAX_LENGTH, padding="max_length", truncation=True,
+                             return_tensors="pt")
+        return tok.input_ids, tok.attention_mask.sum(dim=-1)
+
+    @torch.no_grad()
+    def encode_file(self, prompts_txt_path, encoded_save_path, batch_size: int = 8, store_dtype: str = "float16",
+                    enable_positive_prompt: int = 0) -> dict:
+        """models/Infinity.py:286-335: the .txt's prompts -> {"prompts", "kv_compact_list", "lens_list"}
+        (per-prompt [L_i, C] CPU tensors), saved with torch.save and returned."""
+        if self.encoder is None:
+            raise RuntimeError("T5PromptEncoder: the encoder was dropped")
+        prompts = load_prompts_from_txt(prompts_txt_path)
+        if int(enable_positive_prompt) == 1:
+            prompts = [aug_with_positive_prompt(p) for p in prompts]
+        out_dtype = torch.float16 if store_dtype == "float16" else torch.float32
+        kv_compact_list: List[torch.Tensor] = []
+        lens_list: List[int] = []
+        for start in range(0, len(prompts), int(batch_size)):
+            ids, lens = self.tokenize(prompts[start:start + int(batch_size)])
+            feats = self.encoder(ids, lens).to(torch.float32)        # [B, max(lens), C]
+            for i, li in enumerate(lens.tolist()):
+                kv_compact_list.append(feats[i, :int(li)].to(dtype=out_dtype).cpu())
+                lens_list.append(int(li))
+        payload = {"prompts": prompts, "kv_compact_list": kv_compact_list, "lens_list": lens_list}
+        enc = Path(encoded_save_path)
+        enc.parent.mkdir(parents=True, exist_ok=True)
+        torch.save(payload, enc)
+        return payload
+
+    def drop(self):
+        self.encoder = None
+        if torch.cuda.is_available():
+            torch.cuda.empty_cache()
+
+
 class InfinityES:
     """models/Infinity.py:29-556.  `self.transformer` (= `self.infinity`) is the LoRA target."""
 
@@ -89,7 +167,8 @@ class InfinityES:
             raise ValueError(f"checkpoint_type must be 'torch' or 'torch_shard', got {checkpoint_type}")
         self.arch = a
         self.vae_type = int(vae_type)
-        self.text_tokenizer = self.text_encoder = None
+        self.text_tokenizer = self.text_encoder = self._prompt_encoder = None
+        self.text_encoder_ckpt = text_encoder_ckpt
         self.infinity = InfinityTransformer(a).to(device)
         self.vae = infinity_vae(a).to(device)
         if synthetic_weights:
@@ -115,12 +194,21 @@ class InfinityES:
     # ---- prompt cache (models/Infinity.py:257-349) ---------------------------------------
     def encode_prompts(self, prompts_txt_path, encoded_save_path, batch_size: int = 8, complex_human_instruction=None,
                        overwrite: bool = False, store_dtype: str = "float16"):
+        """models/Infinity.py:257-335.  An existing file loads unless overwrite; else the prompts of the .txt
+        are encoded with the T5 of the local directory text_encoder_ckpt (tokenizer from the same directory)."""
         enc = Path(encoded_save_path)
         if enc.is_file() and not overwrite:
             return torch.load(enc, map_location="cpu", weights_only=True)
-        raise NotImplementedError("the flan-t5-xl text encoder is not available offline; provide an encoded file")
+        if self._prompt_encoder is None or self._prompt_encoder.encoder is None:
+            self._prompt_encoder = T5PromptEncoder(self.text_encoder_ckpt, self.device, self.arch.text_channels)
+            self.text_tokenizer, self.text_encoder = self._prompt_encoder.tokenizer, self._prompt_encoder.encoder
+        return self._prompt_encoder.encode_file(prompts_txt_path, enc, batch_size, store_dtype,
+                                                self.enable_positive_prompt_default)
 
     def drop_text_encoder(self):
+        if self._prompt_encoder is not None:
+            self._prompt_encoder.drop()
+        self._prompt_encoder = None
         self.text_encoder = None
 
     @staticmethod

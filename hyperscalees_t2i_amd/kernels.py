@@ -1138,6 +1138,52 @@ def flash_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: fl
     return out
 
 
+RELBIAS_MAX_N = 512   # RB_NMAX in eggroll_model.hip
+
+
+def relbias_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, rel_bias: torch.Tensor, lens: torch.Tensor,
+                      B: int, N: int, heads: int, scale: float = 1.0,
+                      out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """softmax_{j < lens[b]}(scale * q k^T + rel_bias[h][j - i + R-1]) v on MFMA (eggroll_relbias_attention), head
+    dim 64, N <= 512: the T5 encoder's self-attention.  q / k / v: [>= B*N, >= heads*64] bf16 views with unit inner
+    stride and their own row strides (column slices of one fused qkv GEMM output are read in place); rel_bias
+    [heads, 2R-1] fp32, R >= N, indexed by key - query; lens [B] integer (a CPU tensor is range-checked here
+    and copied; a device tensor is clamped to [0, N] in the kernel).  Rows i >= lens[b] come out zero.
+    Returns [B*N, heads*64] bf16 (or writes `out`)."""
+    for t, nm in ((q, "q"), (k, "k"), (v, "v")):
+        if (not isinstance(t, torch.Tensor) or t.device.type != "cuda" or t.dtype != torch.bfloat16 or t.dim() != 2
+                or t.stride(1) != 1):
+            raise _lib.EggrollError(f"relbias_attention({nm}): expected a 2-D bf16 device view with unit inner stride")
+        if t.shape[0] < B * N or t.shape[1] < heads * 64:
+            raise ValueError(f"relbias_attention: {nm} {tuple(t.shape)} has fewer than B*N={B * N} rows of "
+                             f"heads*64={heads * 64}")
+    if not 1 <= N <= RELBIAS_MAX_N or heads < 1 or B < 0:
+        raise ValueError(f"relbias_attention: need 1 <= N <= {RELBIAS_MAX_N}, heads >= 1, B >= 0 (N={N}, heads={heads}, "
+                         f"B={B})")
+    _dev(rel_bias, "relbias_attention(rel_bias)", torch.float32)
+    if rel_bias.dim() != 2 or rel_bias.shape[0] != heads or rel_bias.shape[1] % 2 != 1 or rel_bias.shape[1] < 2 * N - 1:
+        raise ValueError(f"relbias_attention: rel_bias {tuple(rel_bias.shape)} must be [heads={heads}, 2R-1] with "
+                         f"R >= N={N}")
+    R = (rel_bias.shape[1] + 1) // 2
+    if not isinstance(lens, torch.Tensor) or lens.is_floating_point() or lens.numel() != B:
+        raise ValueError(f"relbias_attention: lens must be an integer tensor of B={B} entries")
+    if lens.device.type == "cpu" and B and (int(lens.min()) < 0 or int(lens.max()) > N):
+        raise ValueError(f"relbias_attention: lens outside [0, {N}]")
+    ln = lens.to(device=q.device, dtype=torch.int32).contiguous()
+    if out is None:
+        out = torch.empty((B * N, heads * 64), dtype=torch.bfloat16, device=q.device)
+    elif (out.device != q.device or out.dtype != torch.bfloat16 or out.dim() != 2 or out.stride(1) != 1
+          or out.shape[0] < B * N or out.shape[1] < heads * 64):
+        raise ValueError("relbias_attention: out must be a bf16 [>= B*N, >= heads*64] device view")
+    e0 = OpTimer.begin()
+    _lib.call("eggroll_relbias_attention", q.data_ptr(), q.stride(0), k.data_ptr(), k.stride(0), v.data_ptr(),
+              v.stride(0), rel_bias.data_ptr(), R, ln.data_ptr(), B, heads, N, 64, float(scale), out.data_ptr(),
+              out.stride(0), _stream(q.device))
+    OpTimer.end(e0, "relbias_attention", 2.0 * 4 * B * N * heads * 64 + 4.0 * rel_bias.numel(), f"B{B} N{N} h{heads}",
+                flops=4.0 * B * heads * N * N * 64)
+    return out
+
+
 def group_norm_nhwc(x: torch.Tensor, groups: int, w: torch.Tensor, b: torch.Tensor, eps: float,
                     silu: bool = False) -> torch.Tensor:
     """GroupNorm over an NHWC bf16 tensor [B, H, W, C] (+ SiLU), fp32 statistics

@@ -481,6 +481,19 @@ int eggroll_flash_attention_sel(const void* q, int64_t q_bs, int64_t ldq, const 
                                 int64_t Lk, int64_t head_dim, float scale, void* o, int64_t o_bs, int64_t ldo, int32_t qf,
                                 void* stream);
 
+/* Attention with a relative-position bias and per-sequence key lengths, head dim 64 (the T5 encoder's
+ * self-attention: transformers T5Attention, position_bias + the key-padding mask as one additive term):
+ *   o[b,i,h,:] = softmax_{j < len[b]}(scale * q[b,i,h,:] . k[b,j,h,:] + rel_bias[h][j - i + R-1]) @ v[b,j,h,:]
+ * q / k / v / o bf16 rows b*N + i with their own row strides, head h at columns h*64 (the [B*N, 3*heads*64]
+ * output of one fused qkv GEMM is read in place); rel_bias fp32 [heads][2R-1], R >= N, indexed by
+ * key - query; lens int32 [B] on the device, clamped to [0, N] in the kernel.  Keys j >= len[b] take no
+ * part and nothing past row N-1 of a sequence is read; query rows i >= len[b] are written as zeros.
+ * head_dim 64 only, 1 <= N <= 512, any heads >= 1; B == 0 is a no-op.  T5 passes scale 1.
+ * Online softmax in fp32, P rounded to bf16 for the PV MFMA.                                          */
+int eggroll_relbias_attention(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv,
+                              const float* rel_bias, int64_t R, const int32_t* lens, int64_t B, int64_t heads,
+                              int64_t N, int64_t head_dim, float scale, void* o, int64_t ldo, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
