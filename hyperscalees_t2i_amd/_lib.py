@@ -92,6 +92,9 @@ SIGNATURES = {
                                           i64, vp, vp, vp, vp, vp]),
     "eggroll_relbias_attention": (C.c_int, [vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, i64, i64, i64, f32, vp, i64,
                                             vp]),
+    "eggroll_softcap_attention": (C.c_int, [vp, i64, vp, i64, vp, i64, vp, i64, i64, i64, i64, i64, f32, f32, vp, i64,
+                                            vp]),
+    "eggroll_rope_half": (C.c_int, [vp, i64, i64, i64, i64, i64, vp, vp, vp]),
 }
 
 _lib = None

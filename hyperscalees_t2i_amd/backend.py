@@ -102,6 +102,9 @@ class SanaConfig:
     # model_name must be a local diffusers directory (transformer/ + vae/, checkpoints.py); True builds
     # `arch` with seeded synthetic weights instead (the benchmark's throughput configuration)
     synthetic_weights: bool = False
+    # auto_encode_if_missing: one local directory with the Gemma-2 checkpoint and its tokenizer files; empty:
+    # model_name/text_encoder + model_name/tokenizer (the diffusers layout)
+    text_encoder_path: str = ""
 
 
 def synthetic_prompt_data(P: int = 4, seq: int = 300, dim: int = 2304, seed: int = 0) -> Dict[str, Any]:
@@ -133,11 +136,24 @@ class SanaBackend(ESBackend):
         return torch.bfloat16 if self.cfg.dtype_latents.lower() == "bfloat16" else torch.float16
 
     def _load_or_encode_prompts(self):
-        """es_backend.py:112-170.  Loads with weights_only=True; no text encoder offline."""
-        if self.cfg.encoded_prompt_path:
-            enc = Path(self.cfg.encoded_prompt_path)
+        """es_backend.py:112-170: an encoded file; with auto_encode_if_missing, that file encoded from
+        prompts_txt_path by the Gemma-2 encoder of model_name (or text_encoder_path) through a SanaOneStep
+        built for encoding only (no transformer, no DC-AE), which is dropped afterwards; or the synthetic set
+        when no path is set.  Loads with weights_only=True."""
+        c = self.cfg
+        if c.encoded_prompt_path:
+            enc = Path(c.encoded_prompt_path)
             if not enc.is_file():
-                raise FileNotFoundError(f"encoded_prompt_path not found and auto_encode unsupported: {enc}")
+                if not c.auto_encode_if_missing:
+                    raise FileNotFoundError(f"encoded_prompt_path not found and auto_encode disabled: {enc}")
+                txt = Path(c.prompts_txt_path)
+                if not txt.is_file():
+                    raise FileNotFoundError(f"prompts_txt_path not found: {txt}")
+                tmp = SanaOneStep(c.model_name, device=self.device, DTYPE=self._dtype(), sigma_data=0.5,
+                                  text_encoder_path=c.text_encoder_path or None, encode_only=True)
+                tmp.encode_prompts(txt, enc, batch_size=int(c.encode_batch_size), overwrite=True)
+                tmp.drop_text_encoder()
+                del tmp
             self.prompt_data = torch.load(enc, map_location="cpu", weights_only=True)
         else:
             self.prompt_data = synthetic_prompt_data(self.cfg.synthetic_prompts)

@@ -717,3 +717,112 @@ def save_t5_encoder(enc, d: Path) -> None:
     st = state_from_build(enc, t5_rules(enc))
     save_file({k: v.detach().cpu().contiguous() for k, v in st.items()}, str(d / T5_WEIGHTS_NAME))
     (d / "config.json").write_text(json.dumps(t5_config_from_arch(enc.arch), indent=2))
+
+
+# ---------------------------------------------------------------------------------------
+# Gemma-2 text model (the gemma-2-2b prompt encoder of the Sana host, models/SanaSprint.py:35-49: the
+# pipeline's text_encoder): a local Hugging Face directory, config.json + model.safetensors (or the sharded
+# form with its index), transformers' key names with or without the `model.` prefix (Gemma2ForCausalLM /
+# Gemma2Model).  lm_head.* is ignored (tied to the embedding); strict otherwise.  Norm weights load into
+# fp32 parameters (gemma2.py), everything else into bf16.  UNPINNED against a real gemma-2-2b directory.
+# ---------------------------------------------------------------------------------------
+GEMMA2_WEIGHTS_NAME = "model.safetensors"
+GEMMA2_WEIGHTS_INDEX = "model.safetensors.index.json"
+GEMMA2_IGNORE = ("lm_head.",)
+
+
+def gemma2_arch_from_config(cfg: dict):
+    """transformers Gemma2Config (config.json) -> Gemma2Arch; refuses what gemma2.py does not build."""
+    from .gemma2 import Gemma2Arch
+    heads = int(cfg["num_attention_heads"])
+    hd = int(cfg.get("head_dim") or int(cfg["hidden_size"]) // heads)
+    if hd != 256:
+        raise NotImplementedError(f"Gemma-2 head_dim={hd} (the attention kernel is head dim 256 only)")
+    act = cfg.get("hidden_activation") or cfg.get("hidden_act", "gelu_pytorch_tanh")
+    if act != "gelu_pytorch_tanh":
+        raise NotImplementedError(f"Gemma-2 hidden_activation={act!r} (only gelu_pytorch_tanh is built)")
+    if cfg.get("attention_bias", False):
+        raise NotImplementedError("Gemma-2 attention_bias=True is not implemented")
+    if cfg.get("use_bidirectional_attention", False):
+        raise NotImplementedError("Gemma-2 use_bidirectional_attention=True is not implemented (causal only)")
+    rope = cfg.get("rope_parameters") or cfg.get("rope_scaling") or {}   # newer transformers nest rope_theta here
+    if rope.get("rope_type", rope.get("type", "default")) != "default":
+        raise NotImplementedError(f"Gemma-2 rope type {rope!r} (only the default rotary embedding is built)")
+    cfg = {**cfg, "rope_theta": cfg.get("rope_theta") or rope.get("rope_theta", 10000.0)}
+    return Gemma2Arch(hidden_size=int(cfg["hidden_size"]), num_layers=int(cfg["num_hidden_layers"]), num_heads=heads,
+                      num_kv_heads=int(cfg.get("num_key_value_heads") or heads), head_dim=hd,
+                      intermediate_size=int(cfg["intermediate_size"]),
+                      softcap=float(cfg.get("attn_logit_softcapping") or 0.0),
+                      query_pre_attn_scalar=float(cfg.get("query_pre_attn_scalar", 256)),
+                      rope_theta=float(cfg.get("rope_theta", 10000.0)), eps=float(cfg.get("rms_norm_eps", 1e-6)),
+                      vocab_size=int(cfg["vocab_size"]), sliding_window=int(cfg.get("sliding_window") or 4096))
+
+
+def gemma2_config_from_arch(a) -> dict:
+    return {"model_type": "gemma2", "architectures": ["Gemma2Model"], "hidden_size": a.hidden_size,
+            "num_hidden_layers": a.num_layers, "num_attention_heads": a.num_heads,
+            "num_key_value_heads": a.num_kv_heads, "head_dim": a.head_dim, "intermediate_size": a.intermediate_size,
+            "attn_logit_softcapping": a.softcap or None, "query_pre_attn_scalar": a.query_pre_attn_scalar,
+            "rope_theta": a.rope_theta, "rms_norm_eps": a.eps, "vocab_size": a.vocab_size,
+            "sliding_window": a.sliding_window, "hidden_activation": "gelu_pytorch_tanh", "attention_bias": False}
+
+
+def gemma2_rules(model: nn.Module, prefix: str = "") -> List[Rule]:
+    """Build parameter <- transformers keys; prefix "" (Gemma2Model) or "model." (Gemma2ForCausalLM)."""
+    def norm(name: str, dkey: str) -> Rule:
+        return (name, [prefix + dkey], lambda ts: ts[0].reshape(1, -1), lambda t: [t.reshape(-1)])
+    rules = [_same("embed", prefix + "embed_tokens.weight"), norm("final_ln", "norm.weight")]
+    qw, kw = model.arch.q_width, model.arch.kv_width
+    for i in range(len(model.blocks)):
+        b, e = f"blocks.{i}", f"{prefix}layers.{i}"
+        rules += [(f"{b}.wqkv", [f"{e}.self_attn.{n}_proj.weight" for n in "qkv"], lambda ts: torch.cat(ts, 0),
+                   lambda t: list(t.split([qw, kw, kw], 0))),
+                  _same(f"{b}.wo", f"{e}.self_attn.o_proj.weight"),
+                  norm(f"{b}.ln_in", f"layers.{i}.input_layernorm.weight"),
+                  norm(f"{b}.ln_post_attn", f"layers.{i}.post_attention_layernorm.weight"),
+                  norm(f"{b}.ln_pre_ff", f"layers.{i}.pre_feedforward_layernorm.weight"),
+                  norm(f"{b}.ln_post_ff", f"layers.{i}.post_feedforward_layernorm.weight"),
+                  _same(f"{b}.w_gate", f"{e}.mlp.gate_proj.weight"), _same(f"{b}.w_up", f"{e}.mlp.up_proj.weight"),
+                  _same(f"{b}.w_down", f"{e}.mlp.down_proj.weight")]
+    return rules
+
+
+def read_gemma2_state(d: Path) -> Dict[str, torch.Tensor]:
+    from safetensors.torch import load_file
+    d = Path(d)
+    if (d / GEMMA2_WEIGHTS_NAME).is_file():
+        return load_file(str(d / GEMMA2_WEIGHTS_NAME))
+    if (d / GEMMA2_WEIGHTS_INDEX).is_file():
+        index = json.loads((d / GEMMA2_WEIGHTS_INDEX).read_text())
+        out: Dict[str, torch.Tensor] = {}
+        for shard in sorted(set(index["weight_map"].values())):
+            out.update(load_file(str(d / shard)))
+        missing = set(index["weight_map"]) - set(out)
+        if missing:
+            raise ValueError(f"{d}: index names tensors absent from its shards: {sorted(missing)[:3]}")
+        return out
+    raise FileNotFoundError(f"{d}: no {GEMMA2_WEIGHTS_NAME} (or {GEMMA2_WEIGHTS_INDEX}) found")
+
+
+def load_gemma2_encoder(d: Path, device="cpu"):
+    """Gemma2Encoder from a local Hugging Face directory (a Gemma2Model's or a Gemma2ForCausalLM's)."""
+    from .gemma2 import Gemma2Encoder
+    d = Path(d)
+    if not d.is_dir():
+        raise FileNotFoundError(f"{d}: not a local Gemma-2 checkpoint directory")
+    enc = Gemma2Encoder(gemma2_arch_from_config(read_config(d))).to(device)
+    state = read_gemma2_state(d)
+    prefix = "model." if any(k.startswith("model.") for k in state) else ""
+    load_into(enc, gemma2_rules(enc, prefix), state, f"{d} (Gemma-2 encoder)", ignore_prefixes=GEMMA2_IGNORE)
+    return enc
+
+
+def save_gemma2_encoder(enc, d: Path, prefix: str = "") -> None:
+    """The build's Gemma-2 weights in transformers' Gemma2Model layout (round trips, tools): norm weights in
+    fp32, the rest in bf16, as the build holds them."""
+    from safetensors.torch import save_file
+    d = Path(d)
+    d.mkdir(parents=True, exist_ok=True)
+    st = state_from_build(enc, gemma2_rules(enc, prefix))
+    save_file({k: v.detach().cpu().contiguous() for k, v in st.items()}, str(d / GEMMA2_WEIGHTS_NAME))
+    (d / "config.json").write_text(json.dumps(gemma2_config_from_arch(enc.arch), indent=2))

@@ -2817,6 +2817,265 @@ extern "C" int eggroll_relbias_attention(const void* q, int64_t ldq, const void*
 }
 
 // ------------------------------------------------------------------------------------
+// Causal attention with a tanh soft-cap on the logits, grouped KV heads and per-sequence key lengths, head
+// dim 256 (the Gemma-2 prompt encoder of Sana):
+//   o[b, i, h, :] = softmax_{j <= i, j < len[b]}(cap > 0 ? cap * tanh(scale * q[b,i,h,:] . k[b,j,h/G,:] / cap)
+//                                                        : scale * q . k) @ v[b, j, h/G, :],  G = heads_q / heads_kv
+// q / k / v / o: rows b*N + i of bf16 matrices with their own row strides, head h at columns 256 h (the
+// output of one fused qkv GEMM is read in place).  k_relbias_attn's scheme at head dim 256: workgroup =
+// (b, query head, 64-query block), 4 waves x 16 queries, S^T = K Q^T so each lane holds 4 keys of ONE query,
+// online softmax in the exp2 domain, the next key block held in registers.  Keys come in blocks of 32: per
+// lane 32 VGPRs of Q fragments, 64 of output accumulators, 32 of prefetch; k + v of a block are
+// 2 x 32 x 264 x 2 B = 33 KB of LDS.  No table over N lives in LDS, so N has no upper limit.  A query block
+// sweeps the key blocks up to its own last query (and below len[b]); a wave skips the arithmetic of a block
+// that lies wholly past its 16 queries (the barriers stay block-uniform); blocks that reach past the wave's
+// first query or past len[b] take -inf where key > query or key >= len[b].  Key 0 is visible to every
+// query of a swept block, so the running max is finite after the first block.  The soft-cap is evaluated in
+// fp32 before the mask as tanh(x) = 1 - 2 / (exp2(2 x log2 e) + 1), which saturates to +-1 without a NaN.
+// Key rows are read clamped to len[b] - 1; query rows >= len[b] are written as zeros.
+// ------------------------------------------------------------------------------------
+constexpr int SC_HD = 256, SC_KB = 32, SC_QB = 64, SC_RS = SC_HD + 8;
+
+__global__ __launch_bounds__(256) void k_softcap_attn(const unsigned short* __restrict__ q, int64_t ldq,
+                                                      const unsigned short* __restrict__ k, int64_t ldk,
+                                                      const unsigned short* __restrict__ v, int64_t ldv,
+                                                      const int* __restrict__ lens, int heads_q, int group, int N,
+                                                      int nqb, float scale_log2, float cap_in, float cap_log2,
+                                                      unsigned short* __restrict__ o, int64_t ldo) {
+    constexpr int KSN = SC_HD / 32, DF = SC_HD / 16, KF = SC_KB / 16, CH = SC_HD / 8;
+    constexpr int UNITS = 2 * SC_KB * CH / 256;   // 16-B chunks of k + v per thread per key block (8)
+    __shared__ __attribute__((aligned(16))) unsigned short sk[SC_KB * SC_RS];
+    __shared__ __attribute__((aligned(16))) unsigned short sv[SC_KB * SC_RS];
+    const int bid = xcd_remap(blockIdx.x, gridDim.x);
+    const int qb = bid % nqb, bh = bid / nqb;
+    const int b = bh / heads_q, h = bh - b * heads_q, hk = h / group;
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, r16 = lane & 15, g = lane >> 4;
+    const int L = min(max(lens[b], 0), N);
+    const int64_t row0 = (int64_t)b * N;
+    if (qb * SC_QB >= L) {   // no valid query in this block (block-uniform): zeros, before any barrier
+#pragma unroll
+        for (int i = 0; i < SC_QB * (SC_HD / 4) / 256; ++i) {
+            const int c = tid + 256 * i, r = c / (SC_HD / 4), cc = c - r * (SC_HD / 4);
+            if (qb * SC_QB + r < N)
+                *reinterpret_cast<u16x4m*>(o + (row0 + qb * SC_QB + r) * ldo + (int64_t)h * SC_HD + 4 * cc) =
+                    u16x4m{0, 0, 0, 0};
+        }
+        return;
+    }
+    const unsigned short* kb_ = k + row0 * ldk + (int64_t)hk * SC_HD;
+    const unsigned short* vb_ = v + row0 * ldv + (int64_t)hk * SC_HD;
+    // Q^T fragments (B operand): dims 32 ks + 8 g .. +7 of query r16 of this wave's 16
+    const int qw0 = qb * SC_QB + w * 16, qr = qw0 + r16;
+    la_bf16x8 bq[KSN];
+#pragma unroll
+    for (int ks = 0; ks < KSN; ++ks) {
+        u16x8m t = u16x8m{0, 0, 0, 0, 0, 0, 0, 0};
+        if (qr < N) t = *reinterpret_cast<const u16x8m*>(q + (row0 + qr) * ldq + (int64_t)h * SC_HD + 32 * ks + 8 * g);
+        bq[ks] = __builtin_bit_cast(la_bf16x8, t);
+    }
+    u16x8m pre[UNITS];
+    auto load_blk = [&](int key0) {
+#pragma unroll
+        for (int i = 0; i < UNITS; ++i) {
+            const int c = tid + 256 * i;             // [k | v][row][chunk]
+            const int kv = c / (SC_KB * CH), rc = c - kv * (SC_KB * CH);
+            const int r = rc / CH, cc = rc - r * CH;
+            // branch-free: rows past L read the last valid key (in bounds) and are zeroed by a select
+            const int row = min(key0 + r, L - 1);
+            const unsigned short* src = kv ? vb_ + (int64_t)row * ldv : kb_ + (int64_t)row * ldk;
+            const u16x8m t = *reinterpret_cast<const u16x8m*>(src + cc * 8);
+            pre[i] = key0 + r < L ? t : u16x8m{0, 0, 0, 0, 0, 0, 0, 0};
+        }
+    };
+    auto store_blk = [&]() {
+#pragma unroll
+        for (int i = 0; i < UNITS; ++i) {
+            const int c = tid + 256 * i;
+            const int kv = c / (SC_KB * CH), rc = c - kv * (SC_KB * CH);
+            const int r = rc / CH, cc = rc - r * CH;
+            *reinterpret_cast<u16x8m*>((kv ? sv : sk) + r * SC_RS + cc * 8) = pre[i];
+        }
+    };
+    la_f32x4 oc[DF];
+#pragma unroll
+    for (int d = 0; d < DF; ++d) oc[d] = la_f32x4{0.f, 0.f, 0.f, 0.f};
+    float m = -INFINITY, l = 0.0f;
+    const int kend = min(L, qb * SC_QB + SC_QB);   // keys [0, kend): causal for the block's last query, below len
+    const int nkb = (kend + SC_KB - 1) / SC_KB;
+    load_blk(0);
+    for (int kb = 0; kb < nkb; ++kb) {
+        __syncthreads();   // every wave is done reading the previous block
+        store_blk();
+        __syncthreads();
+        if (kb + 1 < nkb) load_blk((kb + 1) * SC_KB);   // in flight under this block's MFMAs
+        const int key0 = kb * SC_KB;
+        if (key0 > qw0 + 15) continue;   // wholly past this wave's queries (wave-uniform; barriers are above)
+        la_f32x4 sf[KF];
+#pragma unroll
+        for (int ks = 0; ks < KSN; ++ks) {
+#pragma unroll
+            for (int f = 0; f < KF; ++f) {
+                const la_bf16x8 a = *reinterpret_cast<const la_bf16x8*>(sk + (16 * f + r16) * SC_RS + 32 * ks + 8 * g);
+                sf[f] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, bq[ks], ks ? sf[f] : la_f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
+            }
+        }
+        // t = log2 e * softcap(scale * s); lane: keys key0 + 16 f + 4 g + e of query qr
+        if (cap_log2 > 0.0f) {   // cap_in = 2 log2 e * scale / cap, cap_log2 = log2 e * cap
+#pragma unroll
+            for (int f = 0; f < KF; ++f)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const float ex = __builtin_amdgcn_exp2f(sf[f][e] * cap_in);   // +inf / 0 at the ends: tanh = +-1
+                    sf[f][e] = fmaf(-2.0f * cap_log2, __builtin_amdgcn_rcpf(ex + 1.0f), cap_log2);
+                }
+        } else {
+#pragma unroll
+            for (int f = 0; f < KF; ++f)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) sf[f][e] *= scale_log2;
+        }
+        if (key0 + SC_KB > L || key0 + SC_KB - 1 > qw0) {   // the diagonal / the partial last block (wave-uniform)
+#pragma unroll
+            for (int f = 0; f < KF; ++f)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const int key = key0 + 16 * f + 4 * g + e;
+                    sf[f][e] = (key < L && key <= qr) ? sf[f][e] : -INFINITY;
+                }
+        }
+        float mb = fmaxf(fmaxf(sf[0][0], sf[0][1]), fmaxf(sf[0][2], sf[0][3]));
+#pragma unroll
+        for (int f = 1; f < KF; ++f) mb = fmaxf(fmaxf(mb, fmaxf(sf[f][0], sf[f][1])), fmaxf(sf[f][2], sf[f][3]));
+        mb = g4_max(mb);   // -inf only in a later block with no visible key: then mn = m, finite since block 0
+        const float mn = fmaxf(m, mb);
+        if (__builtin_amdgcn_ballot_w64(mn != m)) {   // a running max moved: rescale
+            const float alpha = __builtin_amdgcn_exp2f(m - mn);   // 0 on the first block (m = -inf)
+            l *= alpha;
+#pragma unroll
+            for (int d = 0; d < DF; ++d)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) oc[d][e] *= alpha;
+            m = mn;
+        }
+        float acc = 0.f;
+#pragma unroll
+        for (int f = 0; f < KF; ++f)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                sf[f][e] = __builtin_amdgcn_exp2f(sf[f][e] - mn);
+                acc += sf[f][e];
+            }
+        l += acc;
+#pragma unroll
+        for (int j = 0; j < KF / 2; ++j) {
+            la_bf16x8 bp;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                bp[e] = (__bf16)sf[2 * j][e];
+                bp[4 + e] = (__bf16)sf[2 * j + 1][e];
+            }
+#pragma unroll
+            for (int d = 0; d < DF; ++d) {
+                const la_bf16x8 av = xa_tr8_perm<SC_RS>(sv + (32 * j) * SC_RS + 16 * d, lane);
+                oc[d] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av, bp, oc[d], 0, 0, 0);
+            }
+        }
+    }
+    const float sum = g4_sum(l);
+    if (qr < N) {
+        const bool valid = qr < L;
+        const float inv = 1.0f / sum;
+        unsigned short* dst = o + (row0 + qr) * ldo + (int64_t)h * SC_HD + 4 * g;
+#pragma unroll
+        for (int d = 0; d < DF; ++d) {
+            u16x4m t;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) t[e] = valid ? f2b(oc[d][e] * inv) : (unsigned short)0;
+            *reinterpret_cast<u16x4m*>(dst + 16 * d) = t;
+        }
+    }
+}
+
+extern "C" int eggroll_softcap_attention(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v,
+                                         int64_t ldv, const int32_t* lens, int64_t B, int64_t heads_q, int64_t heads_kv,
+                                         int64_t N, int64_t head_dim, float scale, float cap, void* o, int64_t ldo,
+                                         void* stream) {
+    EGG_CHECK_ARG(head_dim == SC_HD, "softcap_attention: head_dim %lld unsupported (256)", (long long)head_dim);
+    EGG_CHECK_ARG(B >= 0 && heads_kv >= 1 && heads_q >= heads_kv && heads_q % heads_kv == 0,
+                  "softcap_attention: bad sizes B=%lld heads_q=%lld heads_kv=%lld (heads_q = G * heads_kv)", (long long)B,
+                  (long long)heads_q, (long long)heads_kv);
+    EGG_CHECK_ARG(cap >= 0.0f && cap < INFINITY, "softcap_attention: cap must be finite and >= 0 (0: no soft-cap)");
+    if (B == 0) return EGGROLL_OK;
+    EGG_CHECK_ARG(N >= 1 && N < (1ll << 31) - SC_QB, "softcap_attention: N=%lld outside [1, 2^31 - 64)", (long long)N);
+    EGG_CHECK_ARG(ldq % 8 == 0 && ldk % 8 == 0 && ldv % 8 == 0 && ldo % 4 == 0 && ldq >= heads_q * SC_HD &&
+                  ldk >= heads_kv * SC_HD && ldv >= heads_kv * SC_HD && ldo >= heads_q * SC_HD,
+                  "softcap_attention: bad strides");
+    EGG_CHECK_ARG(q && k && v && o && lens, "softcap_attention: NULL pointer");
+    EGG_CHECK_ARG(((uintptr_t)q & 15) == 0 && ((uintptr_t)k & 15) == 0 && ((uintptr_t)v & 15) == 0 && ((uintptr_t)o & 7) == 0 &&
+                  ((uintptr_t)lens & 3) == 0, "softcap_attention: q/k/v must be 16-byte aligned, o 8-byte aligned");
+    const int64_t nqb = (N + SC_QB - 1) / SC_QB;
+    EGG_CHECK_ARG(B * heads_q * nqb < (1ll << 31), "softcap_attention: grid too large");
+    const float LOG2E = 1.4426950408889634f;
+    hipLaunchKernelGGL(k_softcap_attn, dim3((unsigned)(B * heads_q * nqb)), dim3(256), 0, as_stream(stream),
+                       (const unsigned short*)q, ldq, (const unsigned short*)k, ldk, (const unsigned short*)v, ldv, lens,
+                       (int)heads_q, (int)(heads_q / heads_kv), (int)N, (int)nqb, scale * LOG2E,
+                       cap > 0.0f ? 2.0f * LOG2E * scale / cap : 0.0f, cap * LOG2E, (unsigned short*)o, ldo);
+    EGG_CHECK_LAUNCH("softcap_attention");
+    return EGGROLL_OK;
+}
+
+// ------------------------------------------------------------------------------------
+// Rotate-half RoPE at head dim 256, in place on the q and k columns of a fused qkv GEMM output (Gemma-2):
+//   x[r, 256 h + d]       = x[d] * cos[p, d] - x[d + 128] * sin[p, d]
+//   x[r, 256 h + d + 128] = x[d + 128] * cos[p, d] + x[d] * sin[p, d],   d < 128, p = r % N, h < heads
+// cos / sin: fp32 [N, 128] computed on the host (the two halves of transformers' table are equal), so no
+// angle moves with GPU rounding.  One thread per (row, head, 8 dims of the lower half); fp32 arithmetic.
+// Columns >= 256 heads of a row are not touched.
+// ------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_rope_half(unsigned short* __restrict__ x, int64_t ldx, int64_t rows, int N,
+                                                   int heads, const float* __restrict__ cs,
+                                                   const float* __restrict__ sn) {
+    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int c = (int)(t & 15);
+    const int64_t rh = t >> 4, r = rh / heads;
+    const int h = (int)(rh - r * heads);
+    if (r >= rows) return;
+    const int p = (int)(r % N);
+    unsigned short* px = x + r * ldx + (int64_t)h * 256 + 8 * c;
+    const u16x8m lo = *reinterpret_cast<const u16x8m*>(px), hi = *reinterpret_cast<const u16x8m*>(px + 128);
+    float co[8], si[8];
+    load8f(cs, 1, (int64_t)p * 128 + 8 * c, co);
+    load8f(sn, 1, (int64_t)p * 128 + 8 * c, si);
+    u16x8m ol, oh;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        const float a = b2f(lo[i]), bb = b2f(hi[i]);
+        ol[i] = f2b(a * co[i] - bb * si[i]);
+        oh[i] = f2b(bb * co[i] + a * si[i]);
+    }
+    *reinterpret_cast<u16x8m*>(px) = ol;
+    *reinterpret_cast<u16x8m*>(px + 128) = oh;
+}
+
+extern "C" int eggroll_rope_half(void* x, int64_t ldx, int64_t B, int64_t N, int64_t heads, int64_t head_dim,
+                                 const float* cos_t, const float* sin_t, void* stream) {
+    EGG_CHECK_ARG(head_dim == 256, "rope_half: head_dim %lld unsupported (256)", (long long)head_dim);
+    EGG_CHECK_ARG(B >= 0 && heads >= 1, "rope_half: bad sizes B=%lld heads=%lld", (long long)B, (long long)heads);
+    if (B == 0) return EGGROLL_OK;
+    EGG_CHECK_ARG(N >= 1 && N < (1ll << 31), "rope_half: N=%lld outside [1, 2^31)", (long long)N);
+    EGG_CHECK_ARG(ldx % 8 == 0 && ldx >= heads * 256, "rope_half: bad stride");
+    EGG_CHECK_ARG(x && cos_t && sin_t, "rope_half: NULL pointer");
+    EGG_CHECK_ARG(((uintptr_t)x & 15) == 0 && ((uintptr_t)cos_t & 15) == 0 && ((uintptr_t)sin_t & 15) == 0,
+                  "rope_half: x / cos / sin must be 16-byte aligned");
+    const int64_t nblk = (B * N * heads * 16 + 255) / 256;
+    EGG_CHECK_ARG(nblk < (1ll << 31), "rope_half: grid too large");
+    hipLaunchKernelGGL(k_rope_half, dim3((unsigned)nblk), dim3(256), 0, as_stream(stream), (unsigned short*)x, ldx, B * N,
+                       (int)N, (int)heads, cos_t, sin_t);
+    EGG_CHECK_LAUNCH("rope_half");
+    return EGGROLL_OK;
+}
+
+// ------------------------------------------------------------------------------------
 // GroupNorm (+ SiLU) on NHWC bf16 activations (the FLUX / Infinity VAE decoders' GroupNorm(32)):
 //   y[b, p, c] = act((x - mean[b, g]) * rstd[b, g] * w[c] + bias[c]),  g = c / (C / G),
 // statistics over the H*W pixels and C/G channels of (b, g), biased variance, fp32 data path.

@@ -1184,6 +1184,65 @@ def relbias_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, rel_bia
     return out
 
 
+def softcap_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, lens: torch.Tensor, B: int, N: int,
+                      heads_q: int, heads_kv: int, scale: float, cap: float = 0.0, head_dim: int = 256,
+                      out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """softmax_{j <= i, j < lens[b]}(cap * tanh(scale * q k^T / cap)) v on MFMA (eggroll_softcap_attention), head
+    dim 256, heads_q = G * heads_kv (query head h reads KV head h // G), any N >= 1: Gemma-2's self-attention.
+    cap == 0: no soft-cap (plain causal attention).  q [>= B*N, >= heads_q*256], k / v [>= B*N, >= heads_kv*256]
+    bf16 views with unit inner stride and their own row strides (column slices of one fused qkv GEMM output are
+    read in place); lens [B] integer (a CPU tensor is range-checked here and copied; a device tensor is clamped
+    to [0, N] in the kernel).  Rows i >= lens[b] come out zero.  Returns [B*N, heads_q*256] bf16 (or writes
+    `out`)."""
+    if head_dim != 256:
+        raise ValueError(f"softcap_attention: head_dim {head_dim} unsupported (256)")
+    if B < 0 or N < 1 or heads_kv < 1 or heads_q < heads_kv or heads_q % heads_kv:
+        raise ValueError(f"softcap_attention: need B >= 0, N >= 1, heads_q a multiple of heads_kv >= 1 (B={B}, N={N}, "
+                         f"heads_q={heads_q}, heads_kv={heads_kv})")
+    for t, nm, hh in ((q, "q", heads_q), (k, "k", heads_kv), (v, "v", heads_kv)):
+        if (not isinstance(t, torch.Tensor) or t.device.type != "cuda" or t.dtype != torch.bfloat16 or t.dim() != 2
+                or t.stride(1) != 1):
+            raise _lib.EggrollError(f"softcap_attention({nm}): expected a 2-D bf16 device view with unit inner stride")
+        if t.shape[0] < B * N or t.shape[1] < hh * 256:
+            raise ValueError(f"softcap_attention: {nm} {tuple(t.shape)} has fewer than B*N={B * N} rows of "
+                             f"heads*256={hh * 256}")
+    if not isinstance(lens, torch.Tensor) or lens.is_floating_point() or lens.numel() != B:
+        raise ValueError(f"softcap_attention: lens must be an integer tensor of B={B} entries")
+    if lens.device.type == "cpu" and B and (int(lens.min()) < 0 or int(lens.max()) > N):
+        raise ValueError(f"softcap_attention: lens outside [0, {N}]")
+    ln = lens.to(device=q.device, dtype=torch.int32).contiguous()
+    if out is None:
+        out = torch.empty((B * N, heads_q * 256), dtype=torch.bfloat16, device=q.device)
+    elif (out.device != q.device or out.dtype != torch.bfloat16 or out.dim() != 2 or out.stride(1) != 1
+          or out.shape[0] < B * N or out.shape[1] < heads_q * 256):
+        raise ValueError("softcap_attention: out must be a bf16 [>= B*N, >= heads_q*256] device view")
+    e0 = OpTimer.begin()
+    _lib.call("eggroll_softcap_attention", q.data_ptr(), q.stride(0), k.data_ptr(), k.stride(0), v.data_ptr(),
+              v.stride(0), ln.data_ptr(), B, heads_q, heads_kv, N, 256, float(scale), float(cap), out.data_ptr(),
+              out.stride(0), _stream(q.device))
+    OpTimer.end(e0, "softcap_attention", 2.0 * 2 * B * N * (heads_q + heads_kv) * 256, f"B{B} N{N} h{heads_q}/{heads_kv}",
+                flops=2.0 * B * heads_q * N * N * 256)
+    return out
+
+
+def rope_half_(x: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, B: int, N: int, heads: int) -> torch.Tensor:
+    """In place on the first `heads` 256-wide heads of x [>= B*N, >= heads*256] bf16 (row stride x.stride(0)):
+    rotate-half RoPE with cos / sin [N, 128] fp32 (table row = row % N) — eggroll_rope_half (Gemma-2's q / k).
+    Columns past heads*256 are left as they are."""
+    _dev(x, "rope_half(x)", torch.bfloat16, contiguous=False)
+    _dev(cos, "rope_half(cos)", torch.float32)
+    _dev(sin, "rope_half(sin)", torch.float32)
+    if (x.dim() != 2 or x.stride(1) != 1 or B < 0 or N < 1 or heads < 1 or x.shape[0] < B * N
+            or x.shape[1] < heads * 256 or tuple(cos.shape) != (N, 128) or tuple(sin.shape) != (N, 128)):
+        raise ValueError(f"rope_half: x {tuple(x.shape)}, tables {tuple(cos.shape)} / {tuple(sin.shape)} for B={B}, "
+                         f"N={N}, heads={heads} (x [>= B*N, >= heads*256], tables [N, 128])")
+    e0 = OpTimer.begin()
+    _lib.call("eggroll_rope_half", x.data_ptr(), x.stride(0), B, N, int(heads), 256, cos.data_ptr(), sin.data_ptr(),
+              _stream(x.device))
+    OpTimer.end(e0, "rope_half", 4.0 * B * N * heads * 256, f"rows{B * N}")
+    return x
+
+
 def group_norm_nhwc(x: torch.Tensor, groups: int, w: torch.Tensor, b: torch.Tensor, eps: float,
                     silu: bool = False) -> torch.Tensor:
     """GroupNorm over an NHWC bf16 tensor [B, H, W, C] (+ SiLU), fp32 statistics

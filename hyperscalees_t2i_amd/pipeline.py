@@ -16,7 +16,7 @@ from __future__ import annotations
 
 import math
 from pathlib import Path
-from typing import Any, List, Optional
+from typing import Any, List, Optional, Sequence, Tuple
 
 import torch
 
@@ -43,6 +43,125 @@ class ESBaseModel:
         raise NotImplementedError("Subclasses must implement encode_prompts()")
 
 
+def load_prompts_from_txt(path) -> List[str]:
+    """models/SanaSprint.py:165-169: one prompt per line; blank lines and # lines are skipped."""
+    lines = Path(path).read_text(encoding="utf-8").splitlines()
+    return [ln.strip() for ln in lines if ln.strip() and not ln.strip().startswith("#")]
+
+
+class GemmaPromptEncoder:
+    """The text side of SanaSprintPipeline on its own (diffusers `_get_gemma_prompt_embeds` + `encode_prompt`,
+    clean_caption=False, restated from the published source — PARITY WITH DIFFUSERS UNPINNED, it is not
+    importable here): the tokenizer and the Gemma-2 encoder (gemma2.py) of a local directory.  `model_name` is a
+    diffusers model directory (text_encoder/ + tokenizer/); `text_encoder_path`, when given, is one directory
+    that holds both the checkpoint and the tokenizer files and takes precedence.  Building it never
+    instantiates the Sana transformer or the DC-AE."""
+
+    MAX_SEQUENCE_LENGTH = 300
+
+    def __init__(self, model_name, device: str, text_encoder_path: Optional[str] = None,
+                 caption_channels: Optional[int] = None):
+        if text_encoder_path:
+            enc_dir = tok_dir = Path(str(text_encoder_path))
+            named = str(text_encoder_path)
+        else:
+            enc_dir, tok_dir = Path(str(model_name)) / "text_encoder", Path(str(model_name)) / "tokenizer"
+            named = str(model_name)
+        if not enc_dir.is_dir() or not tok_dir.is_dir():
+            raise FileNotFoundError(f"Sana text encoder {named!r}: not a local directory with "
+                                    f"{'config.json, model.safetensors and the tokenizer files' if text_encoder_path else 'text_encoder/ and tokenizer/'}"
+                                    f" of a Gemma-2 checkpoint (there is no hub access)")
+        from . import checkpoints as ck
+        arch = ck.gemma2_arch_from_config(ck.read_config(enc_dir))
+        if caption_channels is not None and arch.hidden_size != int(caption_channels):
+            raise ValueError(f"{enc_dir}: Gemma-2 hidden_size {arch.hidden_size} != caption_channels "
+                             f"{int(caption_channels)}")
+        from transformers import AutoTokenizer
+        self.tokenizer = AutoTokenizer.from_pretrained(str(tok_dir))
+        self.tokenizer.padding_side = "right"
+        self.device = device
+        self.encoder = ck.load_gemma2_encoder(enc_dir, device)
+
+    @staticmethod
+    def preprocess(prompts: Sequence[str]) -> List[str]:
+        """`_text_preprocessing(clean_caption=False)`: lower-case, strip."""
+        return [str(p).lower().strip() for p in prompts]
+
+    @staticmethod
+    def select_index(max_sequence_length: int = MAX_SEQUENCE_LENGTH) -> List[int]:
+        """Position 0 (BOS), then the last max_sequence_length - 1 positions of the padded sequence."""
+        return [0] + list(range(-max_sequence_length + 1, 0))
+
+    def tokenize(self, prompts: Sequence[str], complex_human_instruction=None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """(input_ids, attention_mask) [B, max_length], right-padded, truncated, with special tokens.  max_length
+        is 300, or with a complex_human_instruction list (joined with newlines and prefixed to every prompt)
+        len(tokenizer.encode(chi)) + 300 - 2."""
+        return tokenize_for_sana(self.tokenizer, prompts, complex_human_instruction, self.MAX_SEQUENCE_LENGTH)
+
+    @torch.no_grad()
+    def encode(self, prompts: Sequence[str], complex_human_instruction=None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """(prompt_embeds [B, 300, C] bf16 on the device, prompt_attention_mask [B, 300] int64 CPU).  Rows the
+        mask marks as padding are zeros."""
+        if self.encoder is None:
+            raise RuntimeError("GemmaPromptEncoder: the encoder was dropped")
+        ids, mask = self.tokenize(prompts, complex_human_instruction)
+        lens = mask.sum(dim=-1)
+        if not torch.equal(mask, (torch.arange(mask.shape[1])[None, :] < lens[:, None]).to(mask.dtype)):
+            raise ValueError("GemmaPromptEncoder: the tokenizer did not pad on the right")
+        h = self.encoder(ids, lens)                                   # [B, N = max(lens), C]; rows >= len: padding
+        B, N, C = h.shape
+        valid = (torch.arange(N)[None, :] < lens[:, None]).to(h.device)
+        full = torch.zeros((B, mask.shape[1], C), dtype=h.dtype, device=h.device)
+        full[:, :N] = h * valid[..., None]
+        sel = self.select_index(self.MAX_SEQUENCE_LENGTH)
+        return full[:, sel], mask[:, sel].to(torch.int64)
+
+    @torch.no_grad()
+    def encode_file(self, prompts_txt_path, encoded_save_path, batch_size: int = 4,
+                    complex_human_instruction=None) -> dict:
+        """models/SanaSprint.py:195-277: the .txt's prompts -> {"prompts", "prompt_embeds" [P, 300, C] fp16 CPU,
+        "prompt_attention_mask" [P, 300] int64 CPU}, saved with torch.save and returned."""
+        prompts = load_prompts_from_txt(prompts_txt_path)
+        if not prompts:
+            raise ValueError(f"{prompts_txt_path}: no prompts (blank and # lines are skipped)")
+        embeds, masks = [], []
+        for start in range(0, len(prompts), max(int(batch_size), 1)):
+            e, m = self.encode(self.preprocess(prompts[start:start + max(int(batch_size), 1)]),
+                               complex_human_instruction)
+            e16 = e.to(torch.float16)
+            if not bool(torch.isfinite(e16).all()):
+                raise RuntimeError(f"GemmaPromptEncoder: prompts {start}..{start + e.shape[0] - 1} do not fit fp16 "
+                                   f"(max |x| = {float(e.float().abs().max()):.3e}); the saved format is float16")
+            embeds.append(e16.cpu())
+            masks.append(m.cpu())
+        payload = {"prompts": prompts, "prompt_embeds": torch.cat(embeds), "prompt_attention_mask": torch.cat(masks)}
+        enc = Path(encoded_save_path)
+        enc.parent.mkdir(parents=True, exist_ok=True)
+        torch.save(payload, enc)
+        return payload
+
+    def drop(self):
+        self.encoder = None
+        if torch.cuda.is_available():
+            torch.cuda.empty_cache()
+
+
+def tokenize_for_sana(tokenizer, prompts: Sequence[str], complex_human_instruction=None,
+                      max_sequence_length: int = 300) -> Tuple[torch.Tensor, torch.Tensor]:
+    """diffusers `_get_gemma_prompt_embeds`' tokenizer call (see GemmaPromptEncoder.tokenize)."""
+    tokenizer.padding_side = "right"
+    prompts = list(prompts)
+    if not complex_human_instruction:
+        max_length = max_sequence_length
+    else:
+        chi = "\n".join(complex_human_instruction)
+        prompts = [chi + p for p in prompts]
+        max_length = len(tokenizer.encode(chi)) + max_sequence_length - 2
+    tok = tokenizer(prompts, padding="max_length", max_length=max_length, truncation=True, add_special_tokens=True,
+                    return_tensors="pt")
+    return tok.input_ids, tok.attention_mask
+
+
 class SanaOneStep(ESBaseModel):
     """models/SanaSprint.py:10-60.  Weights: `model_name` is a LOCAL diffusers-format directory
     (transformer/ + vae/, loaded by checkpoints.py; the architecture comes from its config.json files,
@@ -55,12 +174,21 @@ class SanaOneStep(ESBaseModel):
                  device: str = "cuda:0", DTYPE: torch.dtype = torch.float16, sigma_data: float = 0.5,
                  arch: SanaArch = SANA_SPRINT_1_6B, vae_widths=(128, 256, 512, 512, 1024, 1024),
                  vae_layers=(3, 3, 3, 3, 3, 3), weight_seed: int = 0, vae_chunk: int = 8,
-                 synthetic_weights: bool = False):
+                 synthetic_weights: bool = False, text_encoder_path: Optional[str] = None,
+                 encode_only: bool = False):
+        """text_encoder_path: one local directory with the Gemma-2 checkpoint and its tokenizer files, used by
+        encode_prompts in place of model_name/text_encoder + model_name/tokenizer.  encode_only: build neither
+        the transformer nor the DC-AE (an instance that exists to call encode_prompts)."""
         from . import checkpoints as C
         super().__init__(model_name, device, DTYPE, sigma_data)
         dev = torch.device(device)
         root = Path(str(model_name))
-        if C.is_local_model_dir(str(model_name)):
+        self.text_encoder_path = str(text_encoder_path) if text_encoder_path else None
+        self.tokenizer = self.text_encoder = self._prompt_encoder = None
+        self.vae = None
+        if encode_only:
+            self.weights_source = "none (encode only)"
+        elif C.is_local_model_dir(str(model_name)):
             arch = C.sana_arch_from_config(C.read_config(root / "transformer"))
             vkw = C.dcae_build_kwargs(C.read_config(root / "vae"))
             with torch.device(dev):
@@ -84,6 +212,30 @@ class SanaOneStep(ESBaseModel):
         self.transformer_config = arch
         self.vae_chunk = vae_chunk
         self.ctx = PopulationContext()
+
+    # ---- prompt cache (models/SanaSprint.py:165-277) --------------------------------
+    def encode_prompts(self, prompts_txt_path, encoded_save_path, batch_size: int = 4, complex_human_instruction=None,
+                       overwrite: bool = False):
+        """models/SanaSprint.py:171-277.  An existing file loads unless overwrite; else the prompts of the .txt
+        are encoded as SanaSprintPipeline.encode_prompt(clean_caption=False, max_sequence_length=300) does, by
+        the Gemma-2 encoder and tokenizer of model_name/text_encoder + model_name/tokenizer (or of
+        text_encoder_path), both local.  One difference from the reference: rows past a prompt's length are
+        zeros here, where the reference keeps the model's output for the pad tokens; Sana's cross-attention
+        masks those rows, so nothing downstream sees them."""
+        enc = Path(encoded_save_path)
+        if enc.is_file() and not overwrite:
+            return torch.load(enc, map_location="cpu", weights_only=True)
+        if self._prompt_encoder is None or self._prompt_encoder.encoder is None:
+            cc = self.transformer_config.caption_channels if self.transformer is not None else None
+            self._prompt_encoder = GemmaPromptEncoder(self.model_name, self.device, self.text_encoder_path, cc)
+            self.tokenizer, self.text_encoder = self._prompt_encoder.tokenizer, self._prompt_encoder.encoder
+        return self._prompt_encoder.encode_file(prompts_txt_path, enc, batch_size, complex_human_instruction)
+
+    def drop_text_encoder(self):
+        if self._prompt_encoder is not None:
+            self._prompt_encoder.drop()
+        self._prompt_encoder = None
+        self.text_encoder = None
 
     # ---- shared one-step math -------------------------------------------------------
     def _latents(self, b: int, seed: int, h: int, w: int) -> torch.Tensor:

@@ -494,6 +494,27 @@ int eggroll_relbias_attention(const void* q, int64_t ldq, const void* k, int64_t
                               const float* rel_bias, int64_t R, const int32_t* lens, int64_t B, int64_t heads,
                               int64_t N, int64_t head_dim, float scale, void* o, int64_t ldo, void* stream);
 
+/* Causal attention with a tanh soft-cap on the logits, grouped KV heads and per-sequence key lengths, head
+ * dim 256 (the self-attention of the Gemma-2 prompt encoder of Sana: transformers Gemma2Attention, eager):
+ *   o[b,i,h,:] = softmax_{j <= i, j < len[b]}(cap > 0 ? cap * tanh(scale * q[b,i,h,:] . k[b,j,h/G,:] / cap)
+ *                                                      : scale * q . k) @ v[b,j,h/G,:],  G = heads_q / heads_kv
+ * q / k / v / o bf16 rows b*N + i with their own row strides, head h at columns 256 h (the column slices of
+ * one fused qkv GEMM output are read in place; k / v hold heads_kv heads, q / o heads_q); lens int32 [B] on
+ * the device, clamped to [0, N] in the kernel.  Keys j >= len[b] take no part and nothing past row N-1 of a
+ * sequence is read; query rows i >= len[b] are written as zeros.  head_dim 256 only, heads_q a multiple of
+ * heads_kv, N >= 1 with no upper limit; B == 0 is a no-op; cap == 0 means no soft-cap.  Gemma-2 passes
+ * scale = query_pre_attn_scalar^-1/2.  Soft-cap and online softmax in fp32, P rounded to bf16 for the PV MFMA. */
+int eggroll_softcap_attention(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv,
+                              const int32_t* lens, int64_t B, int64_t heads_q, int64_t heads_kv, int64_t N,
+                              int64_t head_dim, float scale, float cap, void* o, int64_t ldo, void* stream);
+
+/* Rotate-half RoPE at head dim 256, in place on the first `heads` heads of the bf16 rows b*N + i of x (row
+ * stride ldx; the q and k columns of a fused qkv GEMM output; columns >= 256 heads are not touched):
+ *   x[d] <- x[d] cos[i][d] - x[d+128] sin[i][d],  x[d+128] <- x[d+128] cos[i][d] + x[d] sin[i][d],  d < 128
+ * cos_t / sin_t fp32 [N][128], computed by the caller on the host (Gemma2RotaryEmbedding's expressions).  */
+int eggroll_rope_half(void* x, int64_t ldx, int64_t B, int64_t N, int64_t heads, int64_t head_dim,
+                      const float* cos_t, const float* sin_t, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
