@@ -95,6 +95,8 @@ SIGNATURES = {
     "eggroll_softcap_attention": (C.c_int, [vp, i64, vp, i64, vp, i64, vp, i64, i64, i64, i64, i64, f32, f32, vp, i64,
                                             vp]),
     "eggroll_rope_half": (C.c_int, [vp, i64, i64, i64, i64, i64, vp, vp, vp]),
+    "eggroll_causal_attention": (C.c_int, [vp, i64, vp, i64, vp, i64, vp, i64, i64, i64, i64, i64, f32, vp, i64, vp]),
+    "eggroll_qk_norm_rope_half": (C.c_int, [vp, i64, i64, i64, i64, i64, i64, f32, vp, vp, vp, vp, vp]),
 }
 
 _lib = None

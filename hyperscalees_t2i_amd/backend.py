@@ -452,6 +452,9 @@ class ZImageConfig:
     lora_seed: int = 1234
     weight_seed: int = 0
     synthetic_weights: bool = False          # no Z-Image checkpoint loader: True is required (explicit opt-in)
+    # auto_encode_if_missing: one local directory with the Qwen3 checkpoint and its tokenizer files; empty:
+    # model_name/text_encoder + model_name/tokenizer (the diffusers layout)
+    text_encoder_path: str = ""
 
 
 def synthetic_zimage_prompt_data(P: int = 4, lens: Tuple[int, int] = (16, 100), dim: int = 2560,
@@ -478,11 +481,27 @@ class ZImageBackend(ESBackend):
         self.image_pil_mode = 0
 
     def _load_or_encode_prompts(self):
-        """es_backend.py:515-562 (no text encoder offline: an encoded file or the synthetic set)."""
-        if self.cfg.encoded_prompt_path:
-            enc = Path(self.cfg.encoded_prompt_path)
+        """es_backend.py:517-563: an encoded file; with auto_encode_if_missing, that file encoded from
+        prompts_txt_path by the Qwen3 encoder of model_name (or text_encoder_path) through a ZImageTurboES built
+        for encoding only (no transformer, no VAE), which is dropped afterwards; or the synthetic set when no
+        path is set.  Loads with weights_only=True."""
+        c = self.cfg
+        if c.encoded_prompt_path:
+            enc = Path(c.encoded_prompt_path)
             if not enc.is_file():
-                raise FileNotFoundError(f"encoded_prompt_path not found and auto_encode unsupported: {enc}")
+                if not c.auto_encode_if_missing:
+                    raise FileNotFoundError(f"encoded_prompt_path not found and auto_encode disabled: {enc}")
+                txt = Path(c.prompts_txt_path)
+                if not txt.is_file():
+                    raise FileNotFoundError(f"prompts_txt_path not found: {txt}")
+                from .zimage import ZIMAGE_TURBO
+                from .zimage_pipeline import ZImageTurboES
+                arch = self.es_model.arch if self.es_model is not None else (c.arch or ZIMAGE_TURBO)
+                tmp = ZImageTurboES(c.model_name, device=self.device, num_inference_steps=c.num_inference_steps,
+                                    arch=arch, text_encoder_path=c.text_encoder_path or None, encode_only=True)
+                tmp.encode_prompts(txt, enc, batch_size=64, max_sequence_length=512, overwrite=True)
+                tmp.drop_text_encoder()
+                del tmp
             self.prompt_data = torch.load(enc, map_location="cpu", weights_only=True)
         else:
             a = self.es_model.arch if self.es_model is not None else self.cfg.arch

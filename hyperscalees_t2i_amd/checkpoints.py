@@ -826,3 +826,110 @@ def save_gemma2_encoder(enc, d: Path, prefix: str = "") -> None:
     st = state_from_build(enc, gemma2_rules(enc, prefix))
     save_file({k: v.detach().cpu().contiguous() for k, v in st.items()}, str(d / GEMMA2_WEIGHTS_NAME))
     (d / "config.json").write_text(json.dumps(gemma2_config_from_arch(enc.arch), indent=2))
+
+
+# ---------------------------------------------------------------------------------------
+# Qwen3 text model (the Qwen3-4B prompt encoder of the Z-Image host, models/zImageTurbo.py:247-309: the
+# pipeline's text_encoder): a local Hugging Face directory, config.json + model.safetensors (or the sharded
+# form with its index), transformers' key names with or without the `model.` prefix (Qwen3ForCausalLM /
+# Qwen3Model).  The encoder stops at hidden_states[-2], so the last decoder layer's tensors, norm.weight and
+# lm_head.weight are accepted and never loaded; strict otherwise.  Norm weights load into fp32 parameters
+# (qwen3.py: the hidden-size ones as w - 1), everything else into bf16.  UNPINNED against a real Qwen3-4B.
+# ---------------------------------------------------------------------------------------
+QWEN3_WEIGHTS_NAME = "model.safetensors"
+QWEN3_LAYER_TENSORS = tuple(f"{n}.weight" for n in (
+    "self_attn.q_proj", "self_attn.k_proj", "self_attn.v_proj", "self_attn.o_proj", "self_attn.q_norm", "self_attn.k_norm",
+    "mlp.gate_proj", "mlp.up_proj", "mlp.down_proj", "input_layernorm", "post_attention_layernorm"))
+
+
+def qwen3_arch_from_config(cfg: dict):
+    """transformers Qwen3Config (config.json) -> Qwen3Arch; refuses what qwen3.py does not build."""
+    from .qwen3 import Qwen3Arch
+    heads = int(cfg["num_attention_heads"])
+    hd = int(cfg.get("head_dim") or int(cfg["hidden_size"]) // heads)
+    if hd != 128:
+        raise NotImplementedError(f"Qwen3 head_dim={hd} (the attention kernel is head dim 128 only)")
+    if cfg.get("attention_bias", False):
+        raise NotImplementedError("Qwen3 attention_bias=True is not implemented")
+    act = cfg.get("hidden_act", "silu")
+    if act != "silu":
+        raise NotImplementedError(f"Qwen3 hidden_act={act!r} (only silu is built)")
+    rope = cfg.get("rope_parameters") or cfg.get("rope_scaling") or {}   # newer transformers nest rope_theta here
+    if rope.get("rope_type", rope.get("type", "default")) != "default" or rope.get("factor") not in (None, 1, 1.0):
+        raise NotImplementedError(f"Qwen3 rope type / rope_scaling {rope!r} (only the default rotary embedding is built)")
+    if cfg.get("use_sliding_window", False):
+        raise NotImplementedError("Qwen3 use_sliding_window=True is not implemented (full causal attention only)")
+    odd = sorted({str(t) for t in (cfg.get("layer_types") or []) if t != "full_attention"})
+    if odd:
+        raise NotImplementedError(f"Qwen3 layer_types holds {odd} (only full_attention layers are built)")
+    C = int(cfg["hidden_size"])
+    if C % 8 or C > 4096:
+        raise NotImplementedError(f"Qwen3 hidden_size={C} (the norm kernel takes a multiple of 8, at most 4096)")
+    theta = cfg.get("rope_theta") or rope.get("rope_theta", 1e6)
+    return Qwen3Arch(hidden_size=C, num_layers=int(cfg["num_hidden_layers"]), num_heads=heads,
+                     num_kv_heads=int(cfg.get("num_key_value_heads") or heads), head_dim=hd,
+                     intermediate_size=int(cfg["intermediate_size"]), rope_theta=float(theta),
+                     eps=float(cfg.get("rms_norm_eps", 1e-6)), vocab_size=int(cfg["vocab_size"]))
+
+
+def qwen3_config_from_arch(a) -> dict:
+    return {"model_type": "qwen3", "architectures": ["Qwen3Model"], "hidden_size": a.hidden_size,
+            "num_hidden_layers": a.num_layers, "num_attention_heads": a.num_heads,
+            "num_key_value_heads": a.num_kv_heads, "head_dim": a.head_dim, "intermediate_size": a.intermediate_size,
+            "rope_theta": a.rope_theta, "rms_norm_eps": a.eps, "vocab_size": a.vocab_size, "hidden_act": "silu",
+            "attention_bias": False, "use_sliding_window": False}
+
+
+def qwen3_rules(model: nn.Module, prefix: str = "") -> List[Rule]:
+    """Build parameter <- transformers keys; prefix "" (Qwen3Model) or "model." (Qwen3ForCausalLM).  Only the
+    blocks the encoder runs (all but the last layer)."""
+    def norm(name: str, dkey: str) -> Rule:   # rownorm's 1 + mscale operand: w - 1, fp32
+        return (name, [prefix + dkey], lambda ts: ts[0].float().reshape(1, -1) - 1.0, lambda t: [t.reshape(-1) + 1.0])
+
+    def hnorm(name: str, dkey: str) -> Rule:
+        return (name, [prefix + dkey], lambda ts: ts[0].float(), lambda t: [t])
+    rules = [_same("embed", prefix + "embed_tokens.weight")]
+    qw, kw = model.arch.q_width, model.arch.kv_width
+    for i in range(len(model.blocks)):
+        b, e = f"blocks.{i}", f"{prefix}layers.{i}"
+        rules += [(f"{b}.wqkv", [f"{e}.self_attn.{n}_proj.weight" for n in "qkv"], lambda ts: torch.cat(ts, 0),
+                   lambda t: list(t.split([qw, kw, kw], 0))),
+                  hnorm(f"{b}.q_norm", f"layers.{i}.self_attn.q_norm.weight"),
+                  hnorm(f"{b}.k_norm", f"layers.{i}.self_attn.k_norm.weight"),
+                  _same(f"{b}.wo", f"{e}.self_attn.o_proj.weight"),
+                  norm(f"{b}.ln_in", f"layers.{i}.input_layernorm.weight"),
+                  norm(f"{b}.ln_post_attn", f"layers.{i}.post_attention_layernorm.weight"),
+                  _same(f"{b}.w_gate", f"{e}.mlp.gate_proj.weight"), _same(f"{b}.w_up", f"{e}.mlp.up_proj.weight"),
+                  _same(f"{b}.w_down", f"{e}.mlp.down_proj.weight")]
+    return rules
+
+
+def qwen3_unloaded_keys(arch, prefix: str = "") -> set:
+    """Checkpoint tensors the encoder accepts and never loads: the last decoder layer, the final norm, lm_head."""
+    last = f"{prefix}layers.{arch.num_layers - 1}."
+    return {last + n for n in QWEN3_LAYER_TENSORS} | {prefix + "norm.weight", "lm_head.weight"}
+
+
+def load_qwen3_encoder(d: Path, device="cpu"):
+    """Qwen3Encoder from a local Hugging Face directory (a Qwen3Model's or a Qwen3ForCausalLM's)."""
+    from .qwen3 import Qwen3Encoder
+    d = Path(d)
+    if not d.is_dir():
+        raise FileNotFoundError(f"{d}: not a local Qwen3 checkpoint directory")
+    enc = Qwen3Encoder(qwen3_arch_from_config(read_config(d))).to(device)
+    state = read_gemma2_state(d)   # model.safetensors or the sharded form with its index (the same file names)
+    prefix = "model." if any(k.startswith("model.") for k in state) else ""
+    skip = qwen3_unloaded_keys(enc.arch, prefix)
+    load_into(enc, qwen3_rules(enc, prefix), {k: v for k, v in state.items() if k not in skip}, f"{d} (Qwen3 encoder)")
+    return enc
+
+
+def save_qwen3_encoder(enc, d: Path, prefix: str = "") -> None:
+    """The build's Qwen3 weights in transformers' Qwen3Model layout, without the last layer and the final norm
+    it never holds (round trips, tools): norm weights in fp32, the rest in bf16."""
+    from safetensors.torch import save_file
+    d = Path(d)
+    d.mkdir(parents=True, exist_ok=True)
+    st = state_from_build(enc, qwen3_rules(enc, prefix))
+    save_file({k: v.detach().cpu().contiguous() for k, v in st.items()}, str(d / QWEN3_WEIGHTS_NAME))
+    (d / "config.json").write_text(json.dumps(qwen3_config_from_arch(enc.arch), indent=2))

@@ -3076,6 +3076,302 @@ extern "C" int eggroll_rope_half(void* x, int64_t ldx, int64_t B, int64_t N, int
 }
 
 // ------------------------------------------------------------------------------------
+// Causal attention with grouped KV heads and per-sequence key lengths, head dim 128 (the Qwen3 prompt
+// encoder of Z-Image):
+//   o[b, i, h, :] = softmax_{j <= i, j < len[b]}(scale * q[b,i,h,:] . k[b,j,h/G,:]) @ v[b, j, h/G, :],  G = heads_q / heads_kv
+// q / k / v / o: rows b*N + i of bf16 matrices with their own row strides, head h at columns 128 h (the
+// output of one fused qkv GEMM is read in place).  k_flash_attn<2>'s scheme with k_softcap_attn's masks:
+// workgroup = (b, query head, 128-query block), 4 waves x 32 queries (two sets of 16), 64-key blocks of
+// KV head h / G in LDS at row stride 144, the next block held in registers, S^T = K Q^T so each lane holds
+// 4 keys of ONE query, online softmax in base 2 on raw scores, P rounded to bf16, V^T through
+// ds_read_tr16_b64.  The G workgroups of one KV head have adjacent ids under xcd_remap, so their K / V reads
+// meet in one XCD's L2.  A query block sweeps the key blocks that hold a key < min(len[b], its last query +
+// 1); a wave skips the arithmetic of a block wholly past its 32 queries (the barriers stay block-uniform);
+// the j <= i / j < len selects run only in blocks that reach past the wave's first query or past len[b]
+// (wave-uniform branch).  Block 0 is swept first and holds key 0, visible to every query, so a running max
+// is finite before any all-masked block is met: exp2(m - mn) never sees -inf - -inf.  Key rows are read
+// clamped to len[b] - 1; query rows >= len[b] are written as zeros.
+// ------------------------------------------------------------------------------------
+constexpr int CA_QF = 2, CA_QW = 16 * CA_QF, CA_QB = 4 * CA_QW;
+
+__global__ __launch_bounds__(256, 2) void k_causal_attn(const unsigned short* __restrict__ q, int64_t ldq,
+                                                        const unsigned short* __restrict__ k, int64_t ldk,
+                                                        const unsigned short* __restrict__ v, int64_t ldv,
+                                                        const int* __restrict__ lens, int heads_q, int group, int N,
+                                                        int nqb, float scale_log2, unsigned short* __restrict__ o,
+                                                        int64_t ldo) {
+    constexpr int QF = CA_QF, KSN = FA_HD / 32, DF = FA_HD / 16, KF = FA_KB / 16, CH = FA_HD / 8;
+    constexpr int UNITS = 2 * FA_KB * CH / 256;   // 16-B chunks of k + v per thread per key block (8)
+    __shared__ __attribute__((aligned(16))) unsigned short sk[FA_KB * FA_RS];
+    __shared__ __attribute__((aligned(16))) unsigned short sv[FA_KB * FA_RS];
+    const int bid = xcd_remap(blockIdx.x, gridDim.x);
+    const int qb = bid % nqb, bh = bid / nqb;
+    const int b = bh / heads_q, h = bh - b * heads_q, hk = h / group;
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, r16 = lane & 15, g = lane >> 4;
+    const int L = min(max(lens[b], 0), N);
+    const int64_t row0 = (int64_t)b * N;
+    if (qb * CA_QB >= L) {   // no valid query in this block (block-uniform): zeros, before any barrier
+#pragma unroll
+        for (int i = 0; i < CA_QB * (FA_HD / 4) / 256; ++i) {
+            const int c = tid + 256 * i, r = c / (FA_HD / 4), cc = c - r * (FA_HD / 4);
+            if (qb * CA_QB + r < N)
+                *reinterpret_cast<u16x4m*>(o + (row0 + qb * CA_QB + r) * ldo + (int64_t)h * FA_HD + 4 * cc) =
+                    u16x4m{0, 0, 0, 0};
+        }
+        return;
+    }
+    const unsigned short* kb_ = k + row0 * ldk + (int64_t)hk * FA_HD;
+    const unsigned short* vb_ = v + row0 * ldv + (int64_t)hk * FA_HD;
+    // Q^T fragments (B operand): dims 32 ks + 8 g .. +7 of query 16 x + r16 of this wave's 32
+    const int q0 = qb * CA_QB + w * CA_QW;
+    la_bf16x8 bq[QF][KSN];
+#pragma unroll
+    for (int x = 0; x < QF; ++x) {
+        const int qr = q0 + 16 * x + r16;
+#pragma unroll
+        for (int ks = 0; ks < KSN; ++ks) {
+            u16x8m t = u16x8m{0, 0, 0, 0, 0, 0, 0, 0};
+            if (qr < N) t = *reinterpret_cast<const u16x8m*>(q + (row0 + qr) * ldq + (int64_t)h * FA_HD + 32 * ks + 8 * g);
+            bq[x][ks] = __builtin_bit_cast(la_bf16x8, t);
+        }
+    }
+    u16x8m pre[UNITS];
+    auto load_blk = [&](int key0) {
+#pragma unroll
+        for (int i = 0; i < UNITS; ++i) {
+            const int c = tid + 256 * i;             // [k | v][row][chunk]
+            const int kv = c / (FA_KB * CH), rc = c - kv * (FA_KB * CH);
+            const int r = rc / CH, cc = rc - r * CH;
+            // branch-free: rows past L read the last valid key (in bounds) and are zeroed by a select
+            const int row = min(key0 + r, L - 1);
+            const unsigned short* src = kv ? vb_ + (int64_t)row * ldv : kb_ + (int64_t)row * ldk;
+            const u16x8m t = *reinterpret_cast<const u16x8m*>(src + cc * 8);
+            pre[i] = key0 + r < L ? t : u16x8m{0, 0, 0, 0, 0, 0, 0, 0};
+        }
+    };
+    auto store_blk = [&]() {
+#pragma unroll
+        for (int i = 0; i < UNITS; ++i) {
+            const int c = tid + 256 * i;
+            const int kv = c / (FA_KB * CH), rc = c - kv * (FA_KB * CH);
+            const int r = rc / CH, cc = rc - r * CH;
+            *reinterpret_cast<u16x8m*>((kv ? sv : sk) + r * FA_RS + cc * 8) = pre[i];
+        }
+    };
+    la_f32x4 oc[QF][DF];
+    float m[QF], l[QF];
+#pragma unroll
+    for (int x = 0; x < QF; ++x) {
+        m[x] = -INFINITY;
+        l[x] = 0.0f;
+#pragma unroll
+        for (int d = 0; d < DF; ++d) oc[x][d] = la_f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+    const int kend = min(L, qb * CA_QB + CA_QB);   // keys [0, kend): causal for the block's last query, below len
+    const int nkb = (kend + FA_KB - 1) / FA_KB;
+    load_blk(0);
+    for (int kb = 0; kb < nkb; ++kb) {
+        __syncthreads();   // every wave is done reading the previous block
+        store_blk();
+        __syncthreads();
+        if (kb + 1 < nkb) load_blk((kb + 1) * FA_KB);   // in flight under this block's MFMAs
+        const int key0 = kb * FA_KB;
+        if (key0 > q0 + CA_QW - 1) continue;   // wholly past this wave's queries (wave-uniform; barriers are above)
+        la_f32x4 sf[QF][KF];
+#pragma unroll
+        for (int ks = 0; ks < KSN; ++ks) {
+#pragma unroll
+            for (int f = 0; f < KF; ++f) {
+                const la_bf16x8 a = *reinterpret_cast<const la_bf16x8*>(sk + (16 * f + r16) * FA_RS + 32 * ks + 8 * g);
+#pragma unroll
+                for (int x = 0; x < QF; ++x)
+                    sf[x][f] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, bq[x][ks], ks ? sf[x][f] : la_f32x4{0.f, 0.f, 0.f, 0.f},
+                                                                       0, 0, 0);
+            }
+        }
+        // lane: keys key0 + 16 f + 4 g + e of query q0 + 16 x + r16
+        if (key0 + FA_KB > L || key0 + FA_KB - 1 > q0) {   // the diagonal / the partial last block (wave-uniform)
+#pragma unroll
+            for (int f = 0; f < KF; ++f)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const int key = key0 + 16 * f + 4 * g + e;
+#pragma unroll
+                    for (int x = 0; x < QF; ++x)
+                        sf[x][f][e] = (key < L && key <= q0 + 16 * x + r16) ? sf[x][f][e] : -INFINITY;
+                }
+        }
+#pragma unroll
+        for (int x = 0; x < QF; ++x) {
+            float mb = fmaxf(fmaxf(sf[x][0][0], sf[x][0][1]), fmaxf(sf[x][0][2], sf[x][0][3]));
+#pragma unroll
+            for (int f = 1; f < KF; ++f)
+                mb = fmaxf(fmaxf(mb, fmaxf(sf[x][f][0], sf[x][f][1])), fmaxf(sf[x][f][2], sf[x][f][3]));
+            mb = g4_max(mb);   // -inf only in a later block with no visible key: then mn = m, finite since block 0
+            const float mn = fmaxf(m[x], mb * scale_log2);   // scale > 0 commutes with max
+            if (__builtin_amdgcn_ballot_w64(mn != m[x])) {   // a running max moved: rescale this query set
+                const float alpha = __builtin_amdgcn_exp2f(m[x] - mn);   // 0 on the first block (m = -inf)
+                l[x] *= alpha;
+#pragma unroll
+                for (int d = 0; d < DF; ++d)
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) oc[x][d][e] *= alpha;
+                m[x] = mn;
+            }
+            const fa_f32x2 sc2 = {scale_log2, scale_log2}, nm2 = {-mn, -mn};
+            fa_f32x2 acc2 = {0.f, 0.f};
+#pragma unroll
+            for (int f = 0; f < KF; ++f)
+#pragma unroll
+                for (int e = 0; e < 4; e += 2) {
+                    fa_f32x2 t = (fa_f32x2){sf[x][f][e], sf[x][f][e + 1]} * sc2 + nm2;
+                    t.x = __builtin_amdgcn_exp2f(t.x);
+                    t.y = __builtin_amdgcn_exp2f(t.y);
+                    sf[x][f][e] = t.x;
+                    sf[x][f][e + 1] = t.y;
+                    acc2 = acc2 + t;
+                }
+            l[x] += acc2.x + acc2.y;
+        }
+#pragma unroll
+        for (int j = 0; j < KF / 2; ++j) {
+            la_bf16x8 bp[QF];
+#pragma unroll
+            for (int x = 0; x < QF; ++x)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    bp[x][e] = (__bf16)sf[x][2 * j][e];
+                    bp[x][4 + e] = (__bf16)sf[x][2 * j + 1][e];
+                }
+#pragma unroll
+            for (int d = 0; d < DF; ++d) {
+                const la_bf16x8 av = xa_tr8_perm<FA_RS>(sv + (32 * j) * FA_RS + 16 * d, lane);
+#pragma unroll
+                for (int x = 0; x < QF; ++x) oc[x][d] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av, bp[x], oc[x][d], 0, 0, 0);
+            }
+        }
+    }
+#pragma unroll
+    for (int x = 0; x < QF; ++x) {
+        const float sum = g4_sum(l[x]);
+        const int qr = q0 + 16 * x + r16;
+        if (qr < N) {
+            const bool valid = qr < L;
+            const float inv = 1.0f / sum;
+            unsigned short* dst = o + (row0 + qr) * ldo + (int64_t)h * FA_HD + 4 * g;
+#pragma unroll
+            for (int d = 0; d < DF; ++d) {
+                u16x4m t;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) t[e] = valid ? f2b(oc[x][d][e] * inv) : (unsigned short)0;
+                *reinterpret_cast<u16x4m*>(dst + 16 * d) = t;
+            }
+        }
+    }
+}
+
+extern "C" int eggroll_causal_attention(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v,
+                                        int64_t ldv, const int32_t* lens, int64_t B, int64_t heads_q, int64_t heads_kv,
+                                        int64_t N, int64_t head_dim, float scale, void* o, int64_t ldo, void* stream) {
+    EGG_CHECK_ARG(head_dim == FA_HD, "causal_attention: head_dim %lld unsupported (128)", (long long)head_dim);
+    EGG_CHECK_ARG(B >= 0 && heads_kv >= 1 && heads_q >= heads_kv && heads_q % heads_kv == 0,
+                  "causal_attention: bad sizes B=%lld heads_q=%lld heads_kv=%lld (heads_q = G * heads_kv)", (long long)B,
+                  (long long)heads_q, (long long)heads_kv);
+    EGG_CHECK_ARG(scale > 0.0f && scale < INFINITY, "causal_attention: scale must be finite and > 0");
+    if (B == 0) return EGGROLL_OK;
+    EGG_CHECK_ARG(N >= 1 && N < (1ll << 31) - CA_QB, "causal_attention: N=%lld outside [1, 2^31 - 128)", (long long)N);
+    EGG_CHECK_ARG(ldq % 8 == 0 && ldk % 8 == 0 && ldv % 8 == 0 && ldo % 4 == 0 && ldq >= heads_q * FA_HD &&
+                  ldk >= heads_kv * FA_HD && ldv >= heads_kv * FA_HD && ldo >= heads_q * FA_HD,
+                  "causal_attention: bad strides");
+    EGG_CHECK_ARG(q && k && v && o && lens, "causal_attention: NULL pointer");
+    EGG_CHECK_ARG(((uintptr_t)q & 15) == 0 && ((uintptr_t)k & 15) == 0 && ((uintptr_t)v & 15) == 0 && ((uintptr_t)o & 7) == 0 &&
+                  ((uintptr_t)lens & 3) == 0, "causal_attention: q/k/v must be 16-byte aligned, o 8-byte aligned");
+    const int64_t nqb = (N + CA_QB - 1) / CA_QB;
+    EGG_CHECK_ARG(B * heads_q * nqb < (1ll << 31), "causal_attention: grid too large");
+    hipLaunchKernelGGL(k_causal_attn, dim3((unsigned)(B * heads_q * nqb)), dim3(256), 0, as_stream(stream),
+                       (const unsigned short*)q, ldq, (const unsigned short*)k, ldk, (const unsigned short*)v, ldv, lens,
+                       (int)heads_q, (int)(heads_q / heads_kv), (int)N, (int)nqb, scale * 1.4426950408889634f,
+                       (unsigned short*)o, ldo);
+    EGG_CHECK_LAUNCH("causal_attention");
+    return EGGROLL_OK;
+}
+
+// ------------------------------------------------------------------------------------
+// Per-head RMS norm, then rotate-half RoPE, head dim 128, in place on the q | k columns of a fused qkv GEMM
+// output (Qwen3: q_norm / k_norm over head_dim, applied before the rotation):
+//   y = x * rsqrt(mean_128(x^2) + eps) * w[d],   w = wq for heads < heads_q, wk for the next heads_kv
+//   x[r, 128 h + d]      = y[d] * cos[p, d] - y[d + 64] * sin[p, d]
+//   x[r, 128 h + d + 64] = y[d + 64] * cos[p, d] + y[d] * sin[p, d],   d < 64, p = r % N
+// wq / wk fp32 [128]; cos / sin fp32 [N, 64] computed on the host (the two halves of transformers' table are
+// equal), so no angle moves with GPU rounding.  8 lanes per (row, head): each holds 8 dims of the lower
+// half and the 8 dims 64 above them (16-byte loads and stores), the sum of squares goes round the 8 lanes;
+// fp32 arithmetic, one bf16 rounding.  Columns >= 128 (heads_q + heads_kv) of a row are not touched.
+// ------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_qk_norm_rope_half(unsigned short* __restrict__ x, int64_t ldx, int64_t rows,
+                                                           int N, int heads_q, int heads, float eps,
+                                                           const float* __restrict__ wq, const float* __restrict__ wk,
+                                                           const float* __restrict__ cs, const float* __restrict__ sn) {
+    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int c = (int)(t & 7);
+    const int64_t rh = t >> 3, r = rh / heads;
+    const int h = (int)(rh - r * heads);
+    if (r >= rows) return;   // uniform over the 8 lanes of a (row, head)
+    const int p = (int)(r % N);
+    unsigned short* px = x + r * ldx + (int64_t)h * 128 + 8 * c;
+    const u16x8m lo = *reinterpret_cast<const u16x8m*>(px), hi = *reinterpret_cast<const u16x8m*>(px + 64);
+    float a[8], bb[8], ss = 0.0f;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        a[i] = b2f(lo[i]);
+        bb[i] = b2f(hi[i]);
+        ss = fmaf(a[i], a[i], fmaf(bb[i], bb[i], ss));
+    }
+#pragma unroll
+    for (int s = 1; s < 8; s <<= 1) ss += __shfl_xor(ss, s);
+    const float rs = 1.0f / sqrtf(ss * (1.0f / 128.0f) + eps);
+    const float* w = h < heads_q ? wq : wk;
+    float wl[8], wh[8], co[8], si[8];
+    load8f(w, 1, 8 * c, wl);
+    load8f(w, 1, 64 + 8 * c, wh);
+    load8f(cs, 1, (int64_t)p * 64 + 8 * c, co);
+    load8f(sn, 1, (int64_t)p * 64 + 8 * c, si);
+    u16x8m ol, oh;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        const float ya = a[i] * rs * wl[i], yb = bb[i] * rs * wh[i];
+        ol[i] = f2b(ya * co[i] - yb * si[i]);
+        oh[i] = f2b(yb * co[i] + ya * si[i]);
+    }
+    *reinterpret_cast<u16x8m*>(px) = ol;
+    *reinterpret_cast<u16x8m*>(px + 64) = oh;
+}
+
+extern "C" int eggroll_qk_norm_rope_half(void* x, int64_t ldx, int64_t B, int64_t N, int64_t heads_q, int64_t heads_kv,
+                                         int64_t head_dim, float eps, const float* wq, const float* wk,
+                                         const float* cos_t, const float* sin_t, void* stream) {
+    EGG_CHECK_ARG(head_dim == 128, "qk_norm_rope_half: head_dim %lld unsupported (128)", (long long)head_dim);
+    EGG_CHECK_ARG(B >= 0 && heads_q >= 1 && heads_kv >= 1 && heads_q + heads_kv < (1 << 20),
+                  "qk_norm_rope_half: bad sizes B=%lld heads_q=%lld heads_kv=%lld", (long long)B, (long long)heads_q,
+                  (long long)heads_kv);
+    EGG_CHECK_ARG(eps >= 0.0f && eps < INFINITY, "qk_norm_rope_half: eps must be finite and >= 0");
+    if (B == 0) return EGGROLL_OK;
+    const int64_t heads = heads_q + heads_kv;
+    EGG_CHECK_ARG(N >= 1 && N < (1ll << 31), "qk_norm_rope_half: N=%lld outside [1, 2^31)", (long long)N);
+    EGG_CHECK_ARG(ldx % 8 == 0 && ldx >= heads * 128, "qk_norm_rope_half: bad stride");
+    EGG_CHECK_ARG(x && wq && wk && cos_t && sin_t, "qk_norm_rope_half: NULL pointer");
+    EGG_CHECK_ARG(((uintptr_t)x & 15) == 0 && ((uintptr_t)wq & 15) == 0 && ((uintptr_t)wk & 15) == 0 &&
+                  ((uintptr_t)cos_t & 15) == 0 && ((uintptr_t)sin_t & 15) == 0,
+                  "qk_norm_rope_half: x / wq / wk / cos / sin must be 16-byte aligned");
+    EGG_CHECK_ARG(B < (1ll << 31) && B * N < (1ll << 31), "qk_norm_rope_half: too many rows");
+    const int64_t nblk = (B * N * heads * 8 + 255) / 256;
+    EGG_CHECK_ARG(nblk < (1ll << 31), "qk_norm_rope_half: grid too large");
+    hipLaunchKernelGGL(k_qk_norm_rope_half, dim3((unsigned)nblk), dim3(256), 0, as_stream(stream), (unsigned short*)x,
+                       ldx, B * N, (int)N, (int)heads_q, (int)heads, eps, wq, wk, cos_t, sin_t);
+    EGG_CHECK_LAUNCH("qk_norm_rope_half");
+    return EGGROLL_OK;
+}
+
+// ------------------------------------------------------------------------------------
 // GroupNorm (+ SiLU) on NHWC bf16 activations (the FLUX / Infinity VAE decoders' GroupNorm(32)):
 //   y[b, p, c] = act((x - mean[b, g]) * rstd[b, g] * w[c] + bias[c]),  g = c / (C / G),
 // statistics over the H*W pixels and C/G channels of (b, g), biased variance, fp32 data path.

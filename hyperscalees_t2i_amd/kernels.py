@@ -1243,6 +1243,69 @@ def rope_half_(x: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, B: int, N:
     return x
 
 
+def causal_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, lens: torch.Tensor, B: int, N: int,
+                     heads_q: int, heads_kv: int, scale: float, head_dim: int = 128,
+                     out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """softmax_{j <= i, j < lens[b]}(scale * q k^T) v on MFMA (eggroll_causal_attention), head dim 128, heads_q =
+    G * heads_kv (query head h reads KV head h // G), any N >= 1: Qwen3's self-attention.  q [>= B*N, >=
+    heads_q*128], k / v [>= B*N, >= heads_kv*128] bf16 views with unit inner stride and their own row strides
+    (column slices of one fused qkv GEMM output are read in place); lens [B] integer (a CPU tensor is
+    range-checked here and copied; a device tensor is clamped to [0, N] in the kernel).  Rows i >= lens[b] come
+    out zero.  Returns [B*N, heads_q*128] bf16 (or writes `out`)."""
+    if head_dim != 128:
+        raise ValueError(f"causal_attention: head_dim {head_dim} unsupported (128)")
+    if B < 0 or N < 1 or heads_kv < 1 or heads_q < heads_kv or heads_q % heads_kv:
+        raise ValueError(f"causal_attention: need B >= 0, N >= 1, heads_q a multiple of heads_kv >= 1 (B={B}, N={N}, "
+                         f"heads_q={heads_q}, heads_kv={heads_kv})")
+    for t, nm, hh in ((q, "q", heads_q), (k, "k", heads_kv), (v, "v", heads_kv)):
+        if (not isinstance(t, torch.Tensor) or t.device.type != "cuda" or t.dtype != torch.bfloat16 or t.dim() != 2
+                or t.stride(1) != 1):
+            raise _lib.EggrollError(f"causal_attention({nm}): expected a 2-D bf16 device view with unit inner stride")
+        if t.shape[0] < B * N or t.shape[1] < hh * 128:
+            raise ValueError(f"causal_attention: {nm} {tuple(t.shape)} has fewer than B*N={B * N} rows of "
+                             f"heads*128={hh * 128}")
+    if not isinstance(lens, torch.Tensor) or lens.is_floating_point() or lens.numel() != B:
+        raise ValueError(f"causal_attention: lens must be an integer tensor of B={B} entries")
+    if lens.device.type == "cpu" and B and (int(lens.min()) < 0 or int(lens.max()) > N):
+        raise ValueError(f"causal_attention: lens outside [0, {N}]")
+    ln = lens.to(device=q.device, dtype=torch.int32).contiguous()
+    if out is None:
+        out = torch.empty((B * N, heads_q * 128), dtype=torch.bfloat16, device=q.device)
+    elif (out.device != q.device or out.dtype != torch.bfloat16 or out.dim() != 2 or out.stride(1) != 1
+          or out.shape[0] < B * N or out.shape[1] < heads_q * 128):
+        raise ValueError("causal_attention: out must be a bf16 [>= B*N, >= heads_q*128] device view")
+    e0 = OpTimer.begin()
+    _lib.call("eggroll_causal_attention", q.data_ptr(), q.stride(0), k.data_ptr(), k.stride(0), v.data_ptr(),
+              v.stride(0), ln.data_ptr(), B, heads_q, heads_kv, N, 128, float(scale), out.data_ptr(), out.stride(0),
+              _stream(q.device))
+    OpTimer.end(e0, "causal_attention", 2.0 * 2 * B * N * (heads_q + heads_kv) * 128, f"B{B} N{N} h{heads_q}/{heads_kv}",
+                flops=2.0 * B * heads_q * N * N * 128)
+    return out
+
+
+def qk_norm_rope_half_(x: torch.Tensor, wq: torch.Tensor, wk: torch.Tensor, eps: float, cos: torch.Tensor,
+                       sin: torch.Tensor, B: int, N: int, heads_q: int, heads_kv: int) -> torch.Tensor:
+    """In place on the first heads_q + heads_kv 128-wide heads of x [>= B*N, >= (heads_q + heads_kv)*128] bf16
+    (row stride x.stride(0)): per-head RMS norm times wq (the first heads_q heads) or wk (the next heads_kv),
+    both fp32 [128], then rotate-half RoPE with cos / sin [N, 64] fp32 (table row = row % N) —
+    eggroll_qk_norm_rope_half (Qwen3's q / k).  Columns past those heads are left as they are."""
+    _dev(x, "qk_norm_rope_half(x)", torch.bfloat16, contiguous=False)
+    for t, nm in ((wq, "wq"), (wk, "wk"), (cos, "cos"), (sin, "sin")):
+        _dev(t, f"qk_norm_rope_half({nm})", torch.float32)
+    heads = int(heads_q) + int(heads_kv)
+    if (x.dim() != 2 or x.stride(1) != 1 or B < 0 or N < 1 or heads_q < 1 or heads_kv < 1 or x.shape[0] < B * N
+            or x.shape[1] < heads * 128 or tuple(cos.shape) != (N, 64) or tuple(sin.shape) != (N, 64)
+            or wq.numel() != 128 or wk.numel() != 128):
+        raise ValueError(f"qk_norm_rope_half: x {tuple(x.shape)}, wq {tuple(wq.shape)}, wk {tuple(wk.shape)}, tables "
+                         f"{tuple(cos.shape)} / {tuple(sin.shape)} for B={B}, N={N}, heads={heads_q}+{heads_kv} "
+                         f"(x [>= B*N, >= heads*128], weights [128], tables [N, 64])")
+    e0 = OpTimer.begin()
+    _lib.call("eggroll_qk_norm_rope_half", x.data_ptr(), x.stride(0), B, N, int(heads_q), int(heads_kv), 128, float(eps),
+              wq.data_ptr(), wk.data_ptr(), cos.data_ptr(), sin.data_ptr(), _stream(x.device))
+    OpTimer.end(e0, "qk_norm_rope_half", 4.0 * B * N * heads * 128, f"rows{B * N}")
+    return x
+
+
 def group_norm_nhwc(x: torch.Tensor, groups: int, w: torch.Tensor, b: torch.Tensor, eps: float,
                     silu: bool = False) -> torch.Tensor:
     """GroupNorm over an NHWC bf16 tensor [B, H, W, C] (+ SiLU), fp32 statistics

@@ -17,7 +17,8 @@ caption path run once per distinct prompt per member (context refiner), as the S
 """
 from __future__ import annotations
 
-from typing import Any, List, Optional, Sequence, Tuple
+from pathlib import Path
+from typing import Any, Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -41,17 +42,121 @@ def flow_sigmas(steps: int, shift: float = 3.0, num_train: int = 1000,
     return [float(v) for v in sh(s)] + [0.0]
 
 
+def load_prompts_from_txt(path) -> List[str]:
+    """models/zImageTurbo.py:203-205: one prompt per line, stripped; blank lines are skipped.  A # line is a
+    prompt (the Sana and Infinity helpers skip those; Z-Image's does not)."""
+    lines = Path(path).read_text(encoding="utf-8").splitlines()
+    return [ln.strip() for ln in lines if ln.strip()]
+
+
+class QwenPromptEncoder:
+    """The text side of ZImagePipeline on its own (diffusers `ZImagePipeline.encode_prompt` /
+    `_encode_prompt`, do_classifier_free_guidance=False, restated from the published source — PARITY WITH
+    DIFFUSERS UNPINNED, it is not importable here): the tokenizer and the Qwen3 encoder (qwen3.py) of a local
+    directory.  Each prompt goes through the tokenizer's chat template as one user message with the generation
+    prompt and enable_thinking=True, is tokenised padded to max_sequence_length with truncation, and its
+    embedding is hidden_states[-2] of the text encoder on the rows the mask keeps.  `model_name` is a diffusers
+    model directory (text_encoder/ + tokenizer/); `text_encoder_path`, when given, is one directory that holds
+    both the checkpoint and the tokenizer files and takes precedence.  Building it never instantiates the
+    Z-Image transformer or the VAE."""
+
+    def __init__(self, model_name, device: str, text_encoder_path: Optional[str] = None,
+                 cap_feat_dim: Optional[int] = None):
+        if text_encoder_path:
+            enc_dir = tok_dir = Path(str(text_encoder_path))
+            named = str(text_encoder_path)
+        else:
+            enc_dir, tok_dir = Path(str(model_name)) / "text_encoder", Path(str(model_name)) / "tokenizer"
+            named = str(model_name)
+        if not enc_dir.is_dir() or not tok_dir.is_dir():
+            raise FileNotFoundError(f"Z-Image text encoder {named!r}: not a local directory with "
+                                    f"{'config.json, model.safetensors and the tokenizer files' if text_encoder_path else 'text_encoder/ and tokenizer/'}"
+                                    f" of a Qwen3 checkpoint (there is no hub access)")
+        from . import checkpoints as ck
+        arch = ck.qwen3_arch_from_config(ck.read_config(enc_dir))
+        if cap_feat_dim is not None and arch.hidden_size != int(cap_feat_dim):
+            raise ValueError(f"{enc_dir}: Qwen3 hidden_size {arch.hidden_size} != cap_feat_dim {int(cap_feat_dim)}")
+        from transformers import AutoTokenizer
+        self.tokenizer = AutoTokenizer.from_pretrained(str(tok_dir))
+        if not getattr(self.tokenizer, "chat_template", None):
+            raise ValueError(f"{tok_dir}: the tokenizer has no chat_template (ZImagePipeline.encode_prompt formats "
+                             f"every prompt with tokenizer.apply_chat_template)")
+        self.tokenizer.padding_side = "right"
+        self.device = device
+        self.encoder = ck.load_qwen3_encoder(enc_dir, device)
+
+    def template(self, prompts: Sequence[str]) -> List[str]:
+        """Each prompt as one user message, with the generation prompt, enable_thinking=True."""
+        return [self.tokenizer.apply_chat_template([{"role": "user", "content": str(p)}], tokenize=False,
+                                                   add_generation_prompt=True, enable_thinking=True) for p in prompts]
+
+    def tokenize(self, prompts: Sequence[str], max_sequence_length: int = 512) -> Tuple[torch.Tensor, torch.Tensor]:
+        """(input_ids, attention_mask) [B, max_sequence_length] of the templated prompts, right-padded (the
+        tokenizer's own padding side is overridden), truncated."""
+        self.tokenizer.padding_side = "right"
+        tok = self.tokenizer(self.template(prompts), padding="max_length", max_length=int(max_sequence_length),
+                             truncation=True, return_tensors="pt")
+        return tok.input_ids, tok.attention_mask
+
+    @torch.no_grad()
+    def encode(self, prompts: Sequence[str], max_sequence_length: int = 512) -> List[torch.Tensor]:
+        """One [T_i, hidden] bf16 device tensor per prompt: hidden_states[-2] on the rows the mask keeps."""
+        if self.encoder is None:
+            raise RuntimeError("QwenPromptEncoder: the encoder was dropped")
+        if not len(prompts):
+            return []
+        ids, mask = self.tokenize(prompts, max_sequence_length)
+        lens = mask.sum(dim=-1)
+        if not torch.equal(mask, (torch.arange(mask.shape[1])[None, :] < lens[:, None]).to(mask.dtype)):
+            raise ValueError("QwenPromptEncoder: the tokenizer did not pad on the right")
+        h = self.encoder(ids, lens)                                   # [B, N = max(lens), C]; rows >= len: padding
+        return [h[b, :int(L)].clone() for b, L in enumerate(lens.tolist())]
+
+    @torch.no_grad()
+    def encode_file(self, prompts_txt_path, encoded_save_path, batch_size: int = 64,
+                    max_sequence_length: int = 512) -> Dict[str, Any]:
+        """models/zImageTurbo.py:274-304: the .txt's prompts -> {"prompts", "prompt_embeds": a list of [T_i,
+        hidden] bf16 CPU tensors}, saved with torch.save and returned."""
+        prompts = load_prompts_from_txt(prompts_txt_path)
+        if not prompts:
+            raise ValueError(f"{prompts_txt_path}: no prompts (blank lines are skipped)")
+        embeds: List[torch.Tensor] = []
+        step = max(int(batch_size), 1)
+        for start in range(0, len(prompts), step):
+            embeds += [e.to(torch.bfloat16).cpu() for e in self.encode(prompts[start:start + step], max_sequence_length)]
+        payload = {"prompts": prompts, "prompt_embeds": embeds}
+        enc = Path(encoded_save_path)
+        enc.parent.mkdir(parents=True, exist_ok=True)
+        torch.save(payload, enc)
+        return payload
+
+    def drop(self):
+        self.encoder = None
+        if torch.cuda.is_available():
+            torch.cuda.empty_cache()
+
+
 class ZImageTurboES:
     def __init__(self, model_name: str = "Tongyi-MAI/Z-Image-Turbo", device: str = "cuda:0",
                  DTYPE: torch.dtype = torch.bfloat16, num_inference_steps: int = 9, arch: ZImageArch = ZIMAGE_TURBO,
                  vae_widths: Sequence[int] = (128, 256, 512, 512), vae_chunk: int = 16, weight_seed: int = 0,
-                 synthetic_weights: bool = False):
-        from pathlib import Path
-
+                 synthetic_weights: bool = False, text_encoder_path: Optional[str] = None,
+                 encode_only: bool = False):
+        """text_encoder_path: one local directory with the Qwen3 checkpoint and its tokenizer files, used by
+        encode_prompts in place of model_name/text_encoder + model_name/tokenizer.  encode_only: build neither
+        the transformer nor the VAE (an instance that exists to call encode_prompts; `arch` then only names
+        the cap_feat_dim the encoder's width is checked against)."""
         from . import checkpoints as ck
         self.model_name, self.device, self.DTYPE = model_name, device, torch.bfloat16
         self.num_inference_steps = int(num_inference_steps)
-        if synthetic_weights:
+        self.text_encoder_path = str(text_encoder_path) if text_encoder_path else None
+        self.tokenizer = self.text_encoder = self._prompt_encoder = None
+        self.encode_only = bool(encode_only)
+        if encode_only:
+            self.arch = arch
+            self.transformer = self.vae = None
+            self.weights_source = "none (encode only)"
+        elif synthetic_weights:
             self.arch = arch
             self.transformer = ZImageTransformer2DModel(arch).to(device)
             self.transformer.init_weights(weight_seed)
@@ -77,6 +182,38 @@ class ZImageTurboES:
         self.vae_scale_factor = 2 ** (len(vae_widths) - 1)
         self.ctx = PopulationContext()
         self.vae_ctx = PopulationContext()   # theta rows of the decoding members when the VAE decoder has LoRA
+
+    # ---- prompt cache (models/zImageTurbo.py:226-309) -------------------------------
+    def encode_prompts(self, prompts_txt_path, encoded_save_path, batch_size: int = 64, max_sequence_length: int = 512,
+                       overwrite: bool = False, drop_text_encoder_after: bool = True) -> Dict[str, Any]:
+        """models/zImageTurbo.py:247-309.  An existing file loads unless overwrite; else the prompts of the .txt
+        are encoded as ZImagePipeline.encode_prompt(do_classifier_free_guidance=False) does (QwenPromptEncoder:
+        parity with diffusers unpinned) by the Qwen3 encoder and tokenizer of model_name/text_encoder +
+        model_name/tokenizer (or of text_encoder_path), both local.  Saved: {"prompts", "prompt_embeds": a list
+        of [T_i, hidden] bf16 CPU tensors}."""
+        enc = Path(encoded_save_path)
+        if enc.is_file() and not overwrite:
+            data = torch.load(enc, map_location="cpu", weights_only=True)
+        else:
+            if self._prompt_encoder is None or self._prompt_encoder.encoder is None:
+                self._prompt_encoder = QwenPromptEncoder(self.model_name, self.device, self.text_encoder_path,
+                                                         self.arch.cap_feat_dim if self.arch is not None else None)
+                self.tokenizer, self.text_encoder = self._prompt_encoder.tokenizer, self._prompt_encoder.encoder
+            data = self._prompt_encoder.encode_file(prompts_txt_path, enc, batch_size, max_sequence_length)
+        if drop_text_encoder_after:
+            self.drop_text_encoder()
+        return data
+
+    def drop_text_encoder(self):
+        if self._prompt_encoder is not None:
+            self._prompt_encoder.drop()
+        self._prompt_encoder = None
+        self.text_encoder = None
+
+    def _need_generator(self):
+        if self.transformer is None or self.vae is None:
+            raise RuntimeError("ZImageTurboES(encode_only=True) holds no transformer and no VAE: it encodes prompts "
+                               "and cannot generate")
 
     # ---- helpers --------------------------------------------------------------------
     def _check_hw_divisible(self, height_px: int, width_px: int):
@@ -149,6 +286,7 @@ class ZImageTurboES:
                            micro_batch: int = 1, max_sequence_length: int = 512, output_type: str = "pil"):
         """models/zImageTurbo.py:339-407: images for a list of prompt embeddings (micro_batch only chunks
         the reference's pipeline calls; the latents are per-image, so it does not change the result)."""
+        self._need_generator()
         if guidance_scale > 1.0:
             raise NotImplementedError("classifier-free guidance (guidance_scale > 1) is not built; Turbo uses 0.0")
         self._check_hw_divisible(height_px, width_px)
@@ -174,6 +312,7 @@ class ZImageTurboES:
                             num_inference_steps: Optional[int] = None) -> torch.Tensor:
         """All members of theta_pop [n, D] at once: prompt_embeds = the DISTINCT prompts, prompt_index [b]
         image -> distinct prompt.  Returns decoded images [n*b, 3, H, W] (member-major)."""
+        self._need_generator()
         if guidance_scale > 1.0:
             raise NotImplementedError("classifier-free guidance (guidance_scale > 1) is not built; Turbo uses 0.0")
         self._check_hw_divisible(height_px, width_px)

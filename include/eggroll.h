@@ -515,6 +515,30 @@ int eggroll_softcap_attention(const void* q, int64_t ldq, const void* k, int64_t
 int eggroll_rope_half(void* x, int64_t ldx, int64_t B, int64_t N, int64_t heads, int64_t head_dim,
                       const float* cos_t, const float* sin_t, void* stream);
 
+/* Causal attention with grouped KV heads and per-sequence key lengths, head dim 128 (the self-attention of
+ * the Qwen3 prompt encoder of Z-Image: transformers Qwen3Attention, eager):
+ *   o[b,i,h,:] = softmax_{j <= i, j < len[b]}(scale * q[b,i,h,:] . k[b,j,h/G,:]) @ v[b,j,h/G,:],  G = heads_q / heads_kv
+ * q / k / v / o bf16 rows b*N + i with their own row strides, head h at columns 128 h (the column slices of
+ * one fused qkv GEMM output are read in place; k / v hold heads_kv heads, q / o heads_q); lens int32 [B] on
+ * the device, clamped to [0, N] in the kernel.  Keys j >= len[b] take no part and nothing past row N-1 of a
+ * sequence is read; query rows i >= len[b] are written as zeros (len[b] == 0: a whole sequence of zeros).
+ * head_dim 128 only, heads_q a multiple of heads_kv, scale finite and > 0, N >= 1 with no upper limit;
+ * B == 0 is a no-op.  Online softmax in fp32, P rounded to bf16 for the PV MFMA. */
+int eggroll_causal_attention(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv,
+                             const int32_t* lens, int64_t B, int64_t heads_q, int64_t heads_kv, int64_t N,
+                             int64_t head_dim, float scale, void* o, int64_t ldo, void* stream);
+
+/* Per-head RMS norm, then rotate-half RoPE, head dim 128, in place on the first heads_q + heads_kv heads of
+ * the bf16 rows b*N + i of x (row stride ldx; the q | k columns of a fused qkv GEMM output; columns past
+ * them are not touched) — Qwen3's q_norm / k_norm and rotary embedding:
+ *   y = x * rsqrt(mean_128(x^2) + eps) * w[d],  w = wq for the first heads_q heads, wk for the next heads_kv
+ *   y[d] <- y[d] cos[i][d] - y[d+64] sin[i][d],  y[d+64] <- y[d+64] cos[i][d] + y[d] sin[i][d],  d < 64
+ * wq / wk fp32 [128]; cos_t / sin_t fp32 [N][64], computed by the caller on the host (Qwen3RotaryEmbedding's
+ * expressions).  fp32 arithmetic, one bf16 rounding.  B == 0 is a no-op. */
+int eggroll_qk_norm_rope_half(void* x, int64_t ldx, int64_t B, int64_t N, int64_t heads_q, int64_t heads_kv,
+                              int64_t head_dim, float eps, const float* wq, const float* wk, const float* cos_t,
+                              const float* sin_t, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
