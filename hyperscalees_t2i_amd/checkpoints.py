@@ -633,13 +633,69 @@ def save_infinity_checkpoint(model, vae, model_path: Path, vae_path: Path, shard
 
 
 # ---------------------------------------------------------------------------------------
+# What the Hugging Face text-encoder directories (T5, Gemma-2, Qwen3) share: the safetensors reader and
+# writer, the decoder-style config fields and the attention / MLP key rules.
+# ---------------------------------------------------------------------------------------
+HF_WEIGHTS_NAME = "model.safetensors"
+HF_WEIGHTS_INDEX = "model.safetensors.index.json"
+
+
+def read_safetensors_dir(d: Path) -> Dict[str, torch.Tensor]:
+    """model.safetensors of a local Hugging Face directory, or every shard its index names."""
+    from safetensors.torch import load_file
+    d = Path(d)
+    if (d / HF_WEIGHTS_NAME).is_file():
+        return load_file(str(d / HF_WEIGHTS_NAME))
+    if (d / HF_WEIGHTS_INDEX).is_file():
+        index = json.loads((d / HF_WEIGHTS_INDEX).read_text())
+        out: Dict[str, torch.Tensor] = {}
+        for shard in sorted(set(index["weight_map"].values())):
+            out.update(load_file(str(d / shard)))
+        missing = set(index["weight_map"]) - set(out)
+        if missing:
+            raise ValueError(f"{d}: index names tensors absent from its shards: {sorted(missing)[:3]}")
+        return out
+    raise FileNotFoundError(f"{d}: no {HF_WEIGHTS_NAME} (or {HF_WEIGHTS_INDEX}) found")
+
+
+def _save_hf_text_encoder(enc, rules: Sequence[Rule], config: dict, d: Path) -> None:
+    from safetensors.torch import save_file
+    d = Path(d)
+    d.mkdir(parents=True, exist_ok=True)
+    st = state_from_build(enc, rules)
+    save_file({k: v.detach().cpu().contiguous() for k, v in st.items()}, str(d / HF_WEIGHTS_NAME))
+    (d / "config.json").write_text(json.dumps(config, indent=2))
+
+
+def _decoder_attn_config(cfg: dict, what: str, head_dim: int, theta: float) -> Tuple[int, dict, float]:
+    """The fields transformers' Gemma2Config and Qwen3Config share -> (query heads, the rope dict, rope_theta);
+    refuses a head dim other than the attention kernel's, attention_bias and a non-default rope type."""
+    heads = int(cfg["num_attention_heads"])
+    hd = int(cfg.get("head_dim") or int(cfg["hidden_size"]) // heads)
+    if hd != head_dim:
+        raise NotImplementedError(f"{what} head_dim={hd} (the attention kernel is head dim {head_dim} only)")
+    if cfg.get("attention_bias", False):
+        raise NotImplementedError(f"{what} attention_bias=True is not implemented")
+    rope = cfg.get("rope_parameters") or cfg.get("rope_scaling") or {}   # newer transformers nest rope_theta here
+    if rope.get("rope_type", rope.get("type", "default")) != "default":
+        raise NotImplementedError(f"{what} rope type {rope!r} (only the default rotary embedding is built)")
+    return heads, rope, float(cfg.get("rope_theta") or rope.get("rope_theta", theta))
+
+
+def _decoder_layer_rules(b: str, e: str, qw: int, kw: int) -> List[Rule]:
+    """Block `b` <- layer `e` of a Llama-style decoder: q | k | v fused into wqkv, o_proj and the gated MLP."""
+    return [(f"{b}.wqkv", [f"{e}.self_attn.{n}_proj.weight" for n in "qkv"], lambda ts: torch.cat(ts, 0),
+             lambda t: list(t.split([qw, kw, kw], 0))),
+            _same(f"{b}.wo", f"{e}.self_attn.o_proj.weight"), _same(f"{b}.w_gate", f"{e}.mlp.gate_proj.weight"),
+            _same(f"{b}.w_up", f"{e}.mlp.up_proj.weight"), _same(f"{b}.w_down", f"{e}.mlp.down_proj.weight")]
+
+
+# ---------------------------------------------------------------------------------------
 # T5 encoder (the flan-t5-xl prompt encoder of the Infinity host, models/Infinity.py:121-129): a local
 # Hugging Face directory, config.json + model.safetensors (or the sharded form with its index, which is
 # how flan-t5-xl ships), transformers' key names.  The decoder, the LM head and the duplicate
 # encoder.embed_tokens.weight of the full seq2seq checkpoint are ignored by prefix; strict otherwise.
 # ---------------------------------------------------------------------------------------
-T5_WEIGHTS_NAME = "model.safetensors"
-T5_WEIGHTS_INDEX = "model.safetensors.index.json"
 T5_IGNORE = ("decoder.", "lm_head.weight", "encoder.embed_tokens.weight")
 
 
@@ -679,23 +735,11 @@ def t5_rules(model: nn.Module) -> List[Rule]:
 
 
 def read_t5_state(d: Path) -> Dict[str, torch.Tensor]:
-    from safetensors.torch import load_file
     d = Path(d)
-    if (d / T5_WEIGHTS_NAME).is_file():
-        return load_file(str(d / T5_WEIGHTS_NAME))
-    if (d / T5_WEIGHTS_INDEX).is_file():
-        index = json.loads((d / T5_WEIGHTS_INDEX).read_text())
-        out: Dict[str, torch.Tensor] = {}
-        for shard in sorted(set(index["weight_map"].values())):
-            out.update(load_file(str(d / shard)))
-        missing = set(index["weight_map"]) - set(out)
-        if missing:
-            raise ValueError(f"{d}: index names tensors absent from its shards: {sorted(missing)[:3]}")
-        return out
-    if list(d.glob("pytorch_model*.bin")):
+    if not ((d / HF_WEIGHTS_NAME).is_file() or (d / HF_WEIGHTS_INDEX).is_file()) and list(d.glob("pytorch_model*.bin")):
         raise FileNotFoundError(f"{d}: only pytorch_model*.bin found; .bin / pickle T5 checkpoints are not "
-                                f"supported, convert to {T5_WEIGHTS_NAME}")
-    raise FileNotFoundError(f"{d}: no {T5_WEIGHTS_NAME} (or {T5_WEIGHTS_INDEX}) found")
+                                f"supported, convert to {HF_WEIGHTS_NAME}")
+    return read_safetensors_dir(d)
 
 
 def load_t5_encoder(d: Path, device="cpu"):
@@ -711,12 +755,7 @@ def load_t5_encoder(d: Path, device="cpu"):
 
 def save_t5_encoder(enc, d: Path) -> None:
     """The build's T5 encoder weights in transformers' T5EncoderModel layout (round trips, tools)."""
-    from safetensors.torch import save_file
-    d = Path(d)
-    d.mkdir(parents=True, exist_ok=True)
-    st = state_from_build(enc, t5_rules(enc))
-    save_file({k: v.detach().cpu().contiguous() for k, v in st.items()}, str(d / T5_WEIGHTS_NAME))
-    (d / "config.json").write_text(json.dumps(t5_config_from_arch(enc.arch), indent=2))
+    _save_hf_text_encoder(enc, t5_rules(enc), t5_config_from_arch(enc.arch), d)
 
 
 # ---------------------------------------------------------------------------------------
@@ -726,35 +765,24 @@ def save_t5_encoder(enc, d: Path) -> None:
 # Gemma2Model).  lm_head.* is ignored (tied to the embedding); strict otherwise.  Norm weights load into
 # fp32 parameters (gemma2.py), everything else into bf16.  UNPINNED against a real gemma-2-2b directory.
 # ---------------------------------------------------------------------------------------
-GEMMA2_WEIGHTS_NAME = "model.safetensors"
-GEMMA2_WEIGHTS_INDEX = "model.safetensors.index.json"
 GEMMA2_IGNORE = ("lm_head.",)
 
 
 def gemma2_arch_from_config(cfg: dict):
     """transformers Gemma2Config (config.json) -> Gemma2Arch; refuses what gemma2.py does not build."""
     from .gemma2 import Gemma2Arch
-    heads = int(cfg["num_attention_heads"])
-    hd = int(cfg.get("head_dim") or int(cfg["hidden_size"]) // heads)
-    if hd != 256:
-        raise NotImplementedError(f"Gemma-2 head_dim={hd} (the attention kernel is head dim 256 only)")
+    heads, _, theta = _decoder_attn_config(cfg, "Gemma-2", 256, 10000.0)
     act = cfg.get("hidden_activation") or cfg.get("hidden_act", "gelu_pytorch_tanh")
     if act != "gelu_pytorch_tanh":
         raise NotImplementedError(f"Gemma-2 hidden_activation={act!r} (only gelu_pytorch_tanh is built)")
-    if cfg.get("attention_bias", False):
-        raise NotImplementedError("Gemma-2 attention_bias=True is not implemented")
     if cfg.get("use_bidirectional_attention", False):
         raise NotImplementedError("Gemma-2 use_bidirectional_attention=True is not implemented (causal only)")
-    rope = cfg.get("rope_parameters") or cfg.get("rope_scaling") or {}   # newer transformers nest rope_theta here
-    if rope.get("rope_type", rope.get("type", "default")) != "default":
-        raise NotImplementedError(f"Gemma-2 rope type {rope!r} (only the default rotary embedding is built)")
-    cfg = {**cfg, "rope_theta": cfg.get("rope_theta") or rope.get("rope_theta", 10000.0)}
     return Gemma2Arch(hidden_size=int(cfg["hidden_size"]), num_layers=int(cfg["num_hidden_layers"]), num_heads=heads,
-                      num_kv_heads=int(cfg.get("num_key_value_heads") or heads), head_dim=hd,
+                      num_kv_heads=int(cfg.get("num_key_value_heads") or heads), head_dim=256,
                       intermediate_size=int(cfg["intermediate_size"]),
                       softcap=float(cfg.get("attn_logit_softcapping") or 0.0),
                       query_pre_attn_scalar=float(cfg.get("query_pre_attn_scalar", 256)),
-                      rope_theta=float(cfg.get("rope_theta", 10000.0)), eps=float(cfg.get("rms_norm_eps", 1e-6)),
+                      rope_theta=theta, eps=float(cfg.get("rms_norm_eps", 1e-6)),
                       vocab_size=int(cfg["vocab_size"]), sliding_window=int(cfg.get("sliding_window") or 4096))
 
 
@@ -775,33 +803,12 @@ def gemma2_rules(model: nn.Module, prefix: str = "") -> List[Rule]:
     qw, kw = model.arch.q_width, model.arch.kv_width
     for i in range(len(model.blocks)):
         b, e = f"blocks.{i}", f"{prefix}layers.{i}"
-        rules += [(f"{b}.wqkv", [f"{e}.self_attn.{n}_proj.weight" for n in "qkv"], lambda ts: torch.cat(ts, 0),
-                   lambda t: list(t.split([qw, kw, kw], 0))),
-                  _same(f"{b}.wo", f"{e}.self_attn.o_proj.weight"),
-                  norm(f"{b}.ln_in", f"layers.{i}.input_layernorm.weight"),
+        rules += _decoder_layer_rules(b, e, qw, kw)
+        rules += [norm(f"{b}.ln_in", f"layers.{i}.input_layernorm.weight"),
                   norm(f"{b}.ln_post_attn", f"layers.{i}.post_attention_layernorm.weight"),
                   norm(f"{b}.ln_pre_ff", f"layers.{i}.pre_feedforward_layernorm.weight"),
-                  norm(f"{b}.ln_post_ff", f"layers.{i}.post_feedforward_layernorm.weight"),
-                  _same(f"{b}.w_gate", f"{e}.mlp.gate_proj.weight"), _same(f"{b}.w_up", f"{e}.mlp.up_proj.weight"),
-                  _same(f"{b}.w_down", f"{e}.mlp.down_proj.weight")]
+                  norm(f"{b}.ln_post_ff", f"layers.{i}.post_feedforward_layernorm.weight")]
     return rules
-
-
-def read_gemma2_state(d: Path) -> Dict[str, torch.Tensor]:
-    from safetensors.torch import load_file
-    d = Path(d)
-    if (d / GEMMA2_WEIGHTS_NAME).is_file():
-        return load_file(str(d / GEMMA2_WEIGHTS_NAME))
-    if (d / GEMMA2_WEIGHTS_INDEX).is_file():
-        index = json.loads((d / GEMMA2_WEIGHTS_INDEX).read_text())
-        out: Dict[str, torch.Tensor] = {}
-        for shard in sorted(set(index["weight_map"].values())):
-            out.update(load_file(str(d / shard)))
-        missing = set(index["weight_map"]) - set(out)
-        if missing:
-            raise ValueError(f"{d}: index names tensors absent from its shards: {sorted(missing)[:3]}")
-        return out
-    raise FileNotFoundError(f"{d}: no {GEMMA2_WEIGHTS_NAME} (or {GEMMA2_WEIGHTS_INDEX}) found")
 
 
 def load_gemma2_encoder(d: Path, device="cpu"):
@@ -811,7 +818,7 @@ def load_gemma2_encoder(d: Path, device="cpu"):
     if not d.is_dir():
         raise FileNotFoundError(f"{d}: not a local Gemma-2 checkpoint directory")
     enc = Gemma2Encoder(gemma2_arch_from_config(read_config(d))).to(device)
-    state = read_gemma2_state(d)
+    state = read_safetensors_dir(d)
     prefix = "model." if any(k.startswith("model.") for k in state) else ""
     load_into(enc, gemma2_rules(enc, prefix), state, f"{d} (Gemma-2 encoder)", ignore_prefixes=GEMMA2_IGNORE)
     return enc
@@ -820,12 +827,7 @@ def load_gemma2_encoder(d: Path, device="cpu"):
 def save_gemma2_encoder(enc, d: Path, prefix: str = "") -> None:
     """The build's Gemma-2 weights in transformers' Gemma2Model layout (round trips, tools): norm weights in
     fp32, the rest in bf16, as the build holds them."""
-    from safetensors.torch import save_file
-    d = Path(d)
-    d.mkdir(parents=True, exist_ok=True)
-    st = state_from_build(enc, gemma2_rules(enc, prefix))
-    save_file({k: v.detach().cpu().contiguous() for k, v in st.items()}, str(d / GEMMA2_WEIGHTS_NAME))
-    (d / "config.json").write_text(json.dumps(gemma2_config_from_arch(enc.arch), indent=2))
+    _save_hf_text_encoder(enc, gemma2_rules(enc, prefix), gemma2_config_from_arch(enc.arch), d)
 
 
 # ---------------------------------------------------------------------------------------
@@ -836,7 +838,6 @@ def save_gemma2_encoder(enc, d: Path, prefix: str = "") -> None:
 # lm_head.weight are accepted and never loaded; strict otherwise.  Norm weights load into fp32 parameters
 # (qwen3.py: the hidden-size ones as w - 1), everything else into bf16.  UNPINNED against a real Qwen3-4B.
 # ---------------------------------------------------------------------------------------
-QWEN3_WEIGHTS_NAME = "model.safetensors"
 QWEN3_LAYER_TENSORS = tuple(f"{n}.weight" for n in (
     "self_attn.q_proj", "self_attn.k_proj", "self_attn.v_proj", "self_attn.o_proj", "self_attn.q_norm", "self_attn.k_norm",
     "mlp.gate_proj", "mlp.up_proj", "mlp.down_proj", "input_layernorm", "post_attention_layernorm"))
@@ -845,18 +846,12 @@ QWEN3_LAYER_TENSORS = tuple(f"{n}.weight" for n in (
 def qwen3_arch_from_config(cfg: dict):
     """transformers Qwen3Config (config.json) -> Qwen3Arch; refuses what qwen3.py does not build."""
     from .qwen3 import Qwen3Arch
-    heads = int(cfg["num_attention_heads"])
-    hd = int(cfg.get("head_dim") or int(cfg["hidden_size"]) // heads)
-    if hd != 128:
-        raise NotImplementedError(f"Qwen3 head_dim={hd} (the attention kernel is head dim 128 only)")
-    if cfg.get("attention_bias", False):
-        raise NotImplementedError("Qwen3 attention_bias=True is not implemented")
+    heads, rope, theta = _decoder_attn_config(cfg, "Qwen3", 128, 1e6)
+    if rope.get("factor") not in (None, 1, 1.0):
+        raise NotImplementedError(f"Qwen3 rope_scaling {rope!r} (only the default rotary embedding is built)")
     act = cfg.get("hidden_act", "silu")
     if act != "silu":
         raise NotImplementedError(f"Qwen3 hidden_act={act!r} (only silu is built)")
-    rope = cfg.get("rope_parameters") or cfg.get("rope_scaling") or {}   # newer transformers nest rope_theta here
-    if rope.get("rope_type", rope.get("type", "default")) != "default" or rope.get("factor") not in (None, 1, 1.0):
-        raise NotImplementedError(f"Qwen3 rope type / rope_scaling {rope!r} (only the default rotary embedding is built)")
     if cfg.get("use_sliding_window", False):
         raise NotImplementedError("Qwen3 use_sliding_window=True is not implemented (full causal attention only)")
     odd = sorted({str(t) for t in (cfg.get("layer_types") or []) if t != "full_attention"})
@@ -865,10 +860,9 @@ def qwen3_arch_from_config(cfg: dict):
     C = int(cfg["hidden_size"])
     if C % 8 or C > 4096:
         raise NotImplementedError(f"Qwen3 hidden_size={C} (the norm kernel takes a multiple of 8, at most 4096)")
-    theta = cfg.get("rope_theta") or rope.get("rope_theta", 1e6)
     return Qwen3Arch(hidden_size=C, num_layers=int(cfg["num_hidden_layers"]), num_heads=heads,
-                     num_kv_heads=int(cfg.get("num_key_value_heads") or heads), head_dim=hd,
-                     intermediate_size=int(cfg["intermediate_size"]), rope_theta=float(theta),
+                     num_kv_heads=int(cfg.get("num_key_value_heads") or heads), head_dim=128,
+                     intermediate_size=int(cfg["intermediate_size"]), rope_theta=theta,
                      eps=float(cfg.get("rms_norm_eps", 1e-6)), vocab_size=int(cfg["vocab_size"]))
 
 
@@ -892,15 +886,11 @@ def qwen3_rules(model: nn.Module, prefix: str = "") -> List[Rule]:
     qw, kw = model.arch.q_width, model.arch.kv_width
     for i in range(len(model.blocks)):
         b, e = f"blocks.{i}", f"{prefix}layers.{i}"
-        rules += [(f"{b}.wqkv", [f"{e}.self_attn.{n}_proj.weight" for n in "qkv"], lambda ts: torch.cat(ts, 0),
-                   lambda t: list(t.split([qw, kw, kw], 0))),
-                  hnorm(f"{b}.q_norm", f"layers.{i}.self_attn.q_norm.weight"),
+        rules += _decoder_layer_rules(b, e, qw, kw)
+        rules += [hnorm(f"{b}.q_norm", f"layers.{i}.self_attn.q_norm.weight"),
                   hnorm(f"{b}.k_norm", f"layers.{i}.self_attn.k_norm.weight"),
-                  _same(f"{b}.wo", f"{e}.self_attn.o_proj.weight"),
                   norm(f"{b}.ln_in", f"layers.{i}.input_layernorm.weight"),
-                  norm(f"{b}.ln_post_attn", f"layers.{i}.post_attention_layernorm.weight"),
-                  _same(f"{b}.w_gate", f"{e}.mlp.gate_proj.weight"), _same(f"{b}.w_up", f"{e}.mlp.up_proj.weight"),
-                  _same(f"{b}.w_down", f"{e}.mlp.down_proj.weight")]
+                  norm(f"{b}.ln_post_attn", f"layers.{i}.post_attention_layernorm.weight")]
     return rules
 
 
@@ -917,7 +907,7 @@ def load_qwen3_encoder(d: Path, device="cpu"):
     if not d.is_dir():
         raise FileNotFoundError(f"{d}: not a local Qwen3 checkpoint directory")
     enc = Qwen3Encoder(qwen3_arch_from_config(read_config(d))).to(device)
-    state = read_gemma2_state(d)   # model.safetensors or the sharded form with its index (the same file names)
+    state = read_safetensors_dir(d)
     prefix = "model." if any(k.startswith("model.") for k in state) else ""
     skip = qwen3_unloaded_keys(enc.arch, prefix)
     load_into(enc, qwen3_rules(enc, prefix), {k: v for k, v in state.items() if k not in skip}, f"{d} (Qwen3 encoder)")
@@ -927,9 +917,4 @@ def load_qwen3_encoder(d: Path, device="cpu"):
 def save_qwen3_encoder(enc, d: Path, prefix: str = "") -> None:
     """The build's Qwen3 weights in transformers' Qwen3Model layout, without the last layer and the final norm
     it never holds (round trips, tools): norm weights in fp32, the rest in bf16."""
-    from safetensors.torch import save_file
-    d = Path(d)
-    d.mkdir(parents=True, exist_ok=True)
-    st = state_from_build(enc, qwen3_rules(enc, prefix))
-    save_file({k: v.detach().cpu().contiguous() for k, v in st.items()}, str(d / QWEN3_WEIGHTS_NAME))
-    (d / "config.json").write_text(json.dumps(qwen3_config_from_arch(enc.arch), indent=2))
+    _save_hf_text_encoder(enc, qwen3_rules(enc, prefix), qwen3_config_from_arch(enc.arch), d)

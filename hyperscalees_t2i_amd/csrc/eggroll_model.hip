@@ -2624,68 +2624,103 @@ extern "C" int eggroll_flash_attention(const void* q, int64_t q_bs, int64_t ldq,
 }
 
 // ------------------------------------------------------------------------------------
-// Attention with a relative-position bias and per-sequence key lengths, head dim 64 (the T5 encoder):
-//   o[b, i, h, :] = softmax_{j < len[b]}(scale * q[b,i,h,:] . k[b,j,h,:] + rel_bias[h][j - i + R-1]) @ v[b, j, h, :]
-// q / k / v / o: rows b*N + i of bf16 matrices with their own row strides, head h at columns 64 h (the
-// [B*N, 3*heads*64] output of one fused qkv GEMM is read in place).  k_flash_attn's scheme at head dim 64:
-// workgroup = (b, h, 64-query block), 4 waves x 16 queries, keys in blocks of 64 staged in LDS (the next
-// block held in registers), S^T = K Q^T so each lane holds 4 keys of ONE query and the bias index
-// key - query is one subtraction per score.  The head's bias row sits in LDS as sb[d + 511], d = key - query
-// (pre-multiplied by log2 e; zero where |d| >= N, which only padded queries / masked keys reach), so the
-// index needs no clamp for any key / query of a 64-padded N <= 512.  Only the blocks holding keys < len[b]
-// are swept, keys >= len[b] inside the last one take -inf, and key rows are read clamped to len[b] - 1:
-// nothing past row N - 1 of a sequence is touched.  Query rows >= len[b] are written as zeros.
+// Self-attention of the prompt encoders: per-sequence key lengths, q / k / v read in place from one fused
+// qkv GEMM output.  One kernel template, three instances:
+//   o[b, i, h, :] = softmax_{j in keys(b, i)}(t(q[b,i,h,:] . k[b,j,hk,:])) @ v[b, j, hk, :]
+// q / k / v / o: rows b*N + i of bf16 matrices with their own row strides, head h at columns HD h.
+//
+// The sweep is k_flash_attn's: workgroup = (b, query head, 64 QF-query block) under xcd_remap, 4 waves x QF
+// sets of 16 queries; keys in blocks of KB staged in LDS (k and v [KB][RS] bf16) with the next block held in
+// registers while this one computes.  Per key block and wave, MFMA 16x16x32 bf16 with fp32 accumulation:
+//   S^T = K Q^T   (Q^T fragments stay in registers for the whole sweep; each lane: 4 keys of ONE query)
+//   online softmax in base 2: m' = max(m, rowmax), O *= 2^(m - m') only when some lane's max moved,
+//                 P = 2^(t - m'), per-lane partial row sums reduced over the 4 lane groups once at the end
+//   O^T += V^T P^T  (P^T packed to bf16 from the C registers, V^T through ds_read_tr16_b64 in that key order)
+// Only the blocks holding keys < len[b] are swept; keys >= len[b] inside the last one take -inf, and key rows
+// are read clamped to len[b] - 1, so nothing past row N - 1 of a sequence is touched.  Key 0 is visible to
+// every query of a swept block and block 0 is swept first, so every running max is finite after block 0:
+// a later block with no visible key gives rowmax = -inf, m' = m, and exp2(m - m') never sees -inf - -inf.
+// A query block with no query < len[b] writes zeros and leaves before any barrier; every other branch around
+// a barrier is block-uniform.  Query rows >= len[b] are written as zeros.
+//
+// SA_RELBIAS <64, 64, 1, 72> (the T5 encoder): keys(b, i) = {j < len[b]}, hk = h,
+//   t = scale * s + rel_bias[h][j - i + R-1].  The head's bias row sits in LDS as sb[d + 511], d = key - query
+//   (pre-multiplied by log2 e; zero where |d| >= N, which only padded queries / masked keys reach): one
+//   subtraction per score, and no clamp for any key / query of a 64-padded N <= 512 (index in [0, 1022]).
+// SA_SOFTCAP <256, 32, 1, 264> (Gemma-2, Sana): keys(b, i) = {j <= i, j < len[b]}, hk = h / G with
+//   G = heads_q / heads_kv, t = cap > 0 ? cap * tanh(scale * s / cap) : scale * s.  The soft-cap is evaluated
+//   in fp32 before the mask as tanh(x) = 1 - 2 / (exp2(2 x log2 e) + 1), which saturates to +-1 without a NaN.
+//   Per lane 32 VGPRs of Q fragments, 64 of output accumulators, 32 of prefetch; k + v of a 32-key block are
+//   2 x 32 x 264 x 2 B = 33 KB of LDS.  No table over N lives in LDS, so N has no upper limit.
+// SA_CAUSAL <128, 64, 2, 144> (Qwen3, Z-Image): keys and hk as SA_SOFTCAP, t = scale * s; k_flash_attn<2>'s
+//   tile and LDS row stride.  The softmax runs on raw scores: max of raw S (scale > 0 commutes with max), then
+//   p = 2^(s * scale_log2 - m') as one packed FMA per pair.  The G workgroups of one KV head have adjacent ids
+//   under xcd_remap, so their K / V reads meet in one XCD's L2.
+// In the two causal modes a query block sweeps the key blocks that hold a key < min(len[b], its last query +
+// 1); a wave skips the arithmetic of a block wholly past its 16 QF queries (after the block's barriers); the
+// j <= i / j < len selects run only in blocks that reach past the wave's first query or past len[b]
+// (wave-uniform branch).
 // ------------------------------------------------------------------------------------
-constexpr int RB_HD = 64, RB_KB = 64, RB_QB = 64, RB_RS = RB_HD + 8, RB_NMAX = 512;
+enum { SA_RELBIAS = 0, SA_SOFTCAP = 1, SA_CAUSAL = 2 };
+constexpr int RB_NMAX = 512;
 
-__global__ __launch_bounds__(256) void k_relbias_attn(const unsigned short* __restrict__ q, int64_t ldq,
-                                                      const unsigned short* __restrict__ k, int64_t ldk,
-                                                      const unsigned short* __restrict__ v, int64_t ldv,
-                                                      const float* __restrict__ rel_bias, int R,
-                                                      const int* __restrict__ lens, int heads, int N, int nqb,
-                                                      float scale_log2, unsigned short* __restrict__ o, int64_t ldo) {
-    constexpr int KSN = RB_HD / 32, DF = RB_HD / 16, KF = RB_KB / 16, CH = RB_HD / 8;
-    constexpr int UNITS = 2 * RB_KB * CH / 256;   // 16-B chunks of k + v per thread per key block (4)
-    __shared__ __attribute__((aligned(16))) unsigned short sk[RB_KB * RB_RS];
-    __shared__ __attribute__((aligned(16))) unsigned short sv[RB_KB * RB_RS];
-    __shared__ float sb[2 * RB_NMAX];
+template <int MODE, int HD, int KB, int QF, int RS, int MINB>
+__global__ __launch_bounds__(256, MINB) void k_seq_attn(const unsigned short* __restrict__ q, int64_t ldq,
+                                                        const unsigned short* __restrict__ k, int64_t ldk,
+                                                        const unsigned short* __restrict__ v, int64_t ldv,
+                                                        const float* __restrict__ rel_bias, int R,
+                                                        const int* __restrict__ lens, int heads_q, int group, int N,
+                                                        int nqb, float scale_log2, float cap_in, float cap_log2,
+                                                        unsigned short* __restrict__ o, int64_t ldo) {
+    constexpr bool CAUSAL = MODE != SA_RELBIAS;
+    constexpr int QW = 16 * QF, QB = 4 * QW, KSN = HD / 32, DF = HD / 16, KF = KB / 16, CH = HD / 8;
+    constexpr int UNITS = 2 * KB * CH / 256;   // 16-B chunks of k + v per thread per key block
+    __shared__ __attribute__((aligned(16))) unsigned short sk[KB * RS];
+    __shared__ __attribute__((aligned(16))) unsigned short sv[KB * RS];
+    __shared__ float sb[MODE == SA_RELBIAS ? 2 * RB_NMAX : 1];   // SA_RELBIAS only: unused, so no LDS, elsewhere
     const int bid = xcd_remap(blockIdx.x, gridDim.x);
     const int qb = bid % nqb, bh = bid / nqb;
-    const int b = bh / heads, h = bh - b * heads;
+    const int b = bh / heads_q, h = bh - b * heads_q, hk = MODE == SA_RELBIAS ? h : h / group;
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, r16 = lane & 15, g = lane >> 4;
     const int L = min(max(lens[b], 0), N);
     const int64_t row0 = (int64_t)b * N;
-    if (qb * RB_QB >= L) {   // no valid query in this block (block-uniform): zeros, before any barrier
+    if (qb * QB >= L) {   // no valid query in this block (block-uniform): zeros, before any barrier
 #pragma unroll
-        for (int i = 0; i < RB_QB * (RB_HD / 4) / 256; ++i) {
-            const int c = tid + 256 * i, r = c / (RB_HD / 4), cc = c - r * (RB_HD / 4);
-            if (qb * RB_QB + r < N)
-                *reinterpret_cast<u16x4m*>(o + (row0 + qb * RB_QB + r) * ldo + (int64_t)h * RB_HD + 4 * cc) =
+        for (int i = 0; i < QB * (HD / 4) / 256; ++i) {
+            const int c = tid + 256 * i, r = c / (HD / 4), cc = c - r * (HD / 4);
+            if (qb * QB + r < N)
+                *reinterpret_cast<u16x4m*>(o + (row0 + qb * QB + r) * ldo + (int64_t)h * HD + 4 * cc) =
                     u16x4m{0, 0, 0, 0};
         }
         return;
     }
-    for (int t = tid; t < 2 * RB_NMAX; t += 256) {
-        const int d = t - (RB_NMAX - 1);
-        sb[t] = (d > -N && d < N) ? rel_bias[(int64_t)h * (2 * R - 1) + d + (R - 1)] * 1.4426950408889634f : 0.0f;
+    if constexpr (MODE == SA_RELBIAS) {
+        for (int t = tid; t < 2 * RB_NMAX; t += 256) {
+            const int d = t - (RB_NMAX - 1);
+            sb[t] = (d > -N && d < N) ? rel_bias[(int64_t)h * (2 * R - 1) + d + (R - 1)] * 1.4426950408889634f : 0.0f;
+        }
     }
-    const unsigned short* kb_ = k + row0 * ldk + (int64_t)h * RB_HD;
-    const unsigned short* vb_ = v + row0 * ldv + (int64_t)h * RB_HD;
-    // Q^T fragments (B operand): dims 32 ks + 8 g .. +7 of query r16 of this wave's 16
-    const int qr = qb * RB_QB + w * 16 + r16;
-    la_bf16x8 bq[KSN];
+    const unsigned short* kb_ = k + row0 * ldk + (int64_t)hk * HD;
+    const unsigned short* vb_ = v + row0 * ldv + (int64_t)hk * HD;
+    // Q^T fragments (B operand): dims 32 ks + 8 g .. +7 of query 16 x + r16 of this wave's QW
+    const int q0 = qb * QB + w * QW;
+    la_bf16x8 bq[QF][KSN];
 #pragma unroll
-    for (int ks = 0; ks < KSN; ++ks) {
-        u16x8m t = u16x8m{0, 0, 0, 0, 0, 0, 0, 0};
-        if (qr < N) t = *reinterpret_cast<const u16x8m*>(q + (row0 + qr) * ldq + (int64_t)h * RB_HD + 32 * ks + 8 * g);
-        bq[ks] = __builtin_bit_cast(la_bf16x8, t);
+    for (int x = 0; x < QF; ++x) {
+        const int qr = q0 + 16 * x + r16;
+#pragma unroll
+        for (int ks = 0; ks < KSN; ++ks) {
+            u16x8m t = u16x8m{0, 0, 0, 0, 0, 0, 0, 0};
+            if (qr < N) t = *reinterpret_cast<const u16x8m*>(q + (row0 + qr) * ldq + (int64_t)h * HD + 32 * ks + 8 * g);
+            bq[x][ks] = __builtin_bit_cast(la_bf16x8, t);
+        }
     }
     u16x8m pre[UNITS];
     auto load_blk = [&](int key0) {
 #pragma unroll
         for (int i = 0; i < UNITS; ++i) {
             const int c = tid + 256 * i;             // [k | v][row][chunk]
-            const int kv = c / (RB_KB * CH), rc = c - kv * (RB_KB * CH);
+            const int kv = c / (KB * CH), rc = c - kv * (KB * CH);
             const int r = rc / CH, cc = rc - r * CH;
             // branch-free: rows past L read the last valid key (in bounds) and are zeroed by a select
             const int row = min(key0 + r, L - 1);
@@ -2698,330 +2733,251 @@ __global__ __launch_bounds__(256) void k_relbias_attn(const unsigned short* __re
 #pragma unroll
         for (int i = 0; i < UNITS; ++i) {
             const int c = tid + 256 * i;
-            const int kv = c / (RB_KB * CH), rc = c - kv * (RB_KB * CH);
+            const int kv = c / (KB * CH), rc = c - kv * (KB * CH);
             const int r = rc / CH, cc = rc - r * CH;
-            *reinterpret_cast<u16x8m*>((kv ? sv : sk) + r * RB_RS + cc * 8) = pre[i];
+            *reinterpret_cast<u16x8m*>((kv ? sv : sk) + r * RS + cc * 8) = pre[i];
         }
     };
-    la_f32x4 oc[DF];
+    la_f32x4 oc[QF][DF];
+    float m[QF], l[QF];
 #pragma unroll
-    for (int d = 0; d < DF; ++d) oc[d] = la_f32x4{0.f, 0.f, 0.f, 0.f};
-    float m = -INFINITY, l = 0.0f;
-    const int nkb = (L + RB_KB - 1) / RB_KB;
+    for (int x = 0; x < QF; ++x) {
+        m[x] = -INFINITY;
+        l[x] = 0.0f;
+#pragma unroll
+        for (int d = 0; d < DF; ++d) oc[x][d] = la_f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+    // keys [0, kend): below len, and in the causal modes up to the block's last query
+    const int kend = CAUSAL ? min(L, qb * QB + QB) : L;
+    const int nkb = (kend + KB - 1) / KB;
     load_blk(0);
     for (int kb = 0; kb < nkb; ++kb) {
-        __syncthreads();   // every wave is done reading the previous block (first trip: sb is being written)
+        __syncthreads();   // every wave is done reading the previous block (SA_RELBIAS, first trip: sb is being written)
         store_blk();
         __syncthreads();
-        if (kb + 1 < nkb) load_blk((kb + 1) * RB_KB);   // in flight under this block's MFMAs
-        la_f32x4 sf[KF];
+        if (kb + 1 < nkb) load_blk((kb + 1) * KB);   // in flight under this block's MFMAs
+        const int key0 = kb * KB;
+        if (CAUSAL && key0 > q0 + QW - 1) continue;   // wholly past this wave's queries (wave-uniform; barriers are above)
+        la_f32x4 sf[QF][KF];
 #pragma unroll
         for (int ks = 0; ks < KSN; ++ks) {
 #pragma unroll
             for (int f = 0; f < KF; ++f) {
-                const la_bf16x8 a = *reinterpret_cast<const la_bf16x8*>(sk + (16 * f + r16) * RB_RS + 32 * ks + 8 * g);
-                sf[f] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, bq[ks], ks ? sf[f] : la_f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
+                const la_bf16x8 a = *reinterpret_cast<const la_bf16x8*>(sk + (16 * f + r16) * RS + 32 * ks + 8 * g);
+#pragma unroll
+                for (int x = 0; x < QF; ++x)
+                    sf[x][f] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, bq[x][ks], ks ? sf[x][f] : la_f32x4{0.f, 0.f, 0.f, 0.f},
+                                                                       0, 0, 0);
             }
         }
-        const int key0 = kb * RB_KB;
-        // t = log2 e * (scale * s + bias[key - query]); lane: keys key0 + 16 f + 4 g + e of query qr.
-        // key <= 511 and qr <= 511 (64-padded N <= 512), so the index lies in [0, 1022]
-        const float* bl = sb + (key0 + 4 * g - qr + (RB_NMAX - 1));
+        // the score transform; lane: keys key0 + 16 f + 4 g + e of query q0 + 16 x + r16
+        if constexpr (MODE == SA_RELBIAS) {
+            // t = log2 e * (scale * s + bias[key - query]); key <= 511 and query <= 511 (64-padded N <= 512), so
+            // the index lies in [0, 1022]
 #pragma unroll
-        for (int f = 0; f < KF; ++f)
+            for (int x = 0; x < QF; ++x) {
+                const float* bl = sb + (key0 + 4 * g - (q0 + 16 * x + r16) + (RB_NMAX - 1));
 #pragma unroll
-            for (int e = 0; e < 4; ++e) sf[f][e] = fmaf(sf[f][e], scale_log2, bl[16 * f + e]);
-        if (key0 + RB_KB > L) {   // the partial last block: keys >= L -> -inf (uniform branch)
+                for (int f = 0; f < KF; ++f)
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) sf[x][f][e] = fmaf(sf[x][f][e], scale_log2, bl[16 * f + e]);
+            }
+        } else if constexpr (MODE == SA_SOFTCAP) {
+            // t = log2 e * softcap(scale * s)
+            if (cap_log2 > 0.0f) {   // cap_in = 2 log2 e * scale / cap, cap_log2 = log2 e * cap
+#pragma unroll
+                for (int x = 0; x < QF; ++x)
+#pragma unroll
+                    for (int f = 0; f < KF; ++f)
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) {
+                            const float ex = __builtin_amdgcn_exp2f(sf[x][f][e] * cap_in);   // +inf / 0 at the ends: tanh = +-1
+                            sf[x][f][e] = fmaf(-2.0f * cap_log2, __builtin_amdgcn_rcpf(ex + 1.0f), cap_log2);
+                        }
+            } else {
+#pragma unroll
+                for (int x = 0; x < QF; ++x)
+#pragma unroll
+                    for (int f = 0; f < KF; ++f)
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) sf[x][f][e] *= scale_log2;
+            }
+        }   // SA_CAUSAL: none, the scale is folded into the exp below
+        // the partial last block, and in the causal modes the diagonal (wave-uniform branch)
+        if (key0 + KB > L || (CAUSAL && key0 + KB - 1 > q0)) {
 #pragma unroll
             for (int f = 0; f < KF; ++f)
 #pragma unroll
-                for (int e = 0; e < 4; ++e) sf[f][e] = key0 + 16 * f + 4 * g + e < L ? sf[f][e] : -INFINITY;
+                for (int e = 0; e < 4; ++e) {
+                    const int key = key0 + 16 * f + 4 * g + e;
+#pragma unroll
+                    for (int x = 0; x < QF; ++x)
+                        sf[x][f][e] = (key < L && (!CAUSAL || key <= q0 + 16 * x + r16)) ? sf[x][f][e] : -INFINITY;
+                }
         }
-        float mb = fmaxf(fmaxf(sf[0][0], sf[0][1]), fmaxf(sf[0][2], sf[0][3]));
 #pragma unroll
-        for (int f = 1; f < KF; ++f) mb = fmaxf(fmaxf(mb, fmaxf(sf[f][0], sf[f][1])), fmaxf(sf[f][2], sf[f][3]));
-        mb = g4_max(mb);   // finite: key key0 of every swept block is < L
-        const float mn = fmaxf(m, mb);
-        if (__builtin_amdgcn_ballot_w64(mn != m)) {   // a running max moved: rescale
-            const float alpha = __builtin_amdgcn_exp2f(m - mn);   // 0 on the first block (m = -inf)
-            l *= alpha;
+        for (int x = 0; x < QF; ++x) {
+            float mb = fmaxf(fmaxf(sf[x][0][0], sf[x][0][1]), fmaxf(sf[x][0][2], sf[x][0][3]));
 #pragma unroll
-            for (int d = 0; d < DF; ++d)
+            for (int f = 1; f < KF; ++f)
+                mb = fmaxf(fmaxf(mb, fmaxf(sf[x][f][0], sf[x][f][1])), fmaxf(sf[x][f][2], sf[x][f][3]));
+            mb = g4_max(mb);   // -inf only in a later block with no visible key: then mn = m, finite since block 0
+            const float mn = fmaxf(m[x], MODE == SA_CAUSAL ? mb * scale_log2 : mb);   // scale > 0 commutes with max
+            if (__builtin_amdgcn_ballot_w64(mn != m[x])) {   // a running max moved: rescale this query set
+                const float alpha = __builtin_amdgcn_exp2f(m[x] - mn);   // 0 on the first block (m = -inf)
+                l[x] *= alpha;
 #pragma unroll
-                for (int e = 0; e < 4; ++e) oc[d][e] *= alpha;
-            m = mn;
-        }
-        float acc = 0.f;
+                for (int d = 0; d < DF; ++d)
 #pragma unroll
-        for (int f = 0; f < KF; ++f)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                sf[f][e] = __builtin_amdgcn_exp2f(sf[f][e] - mn);
-                acc += sf[f][e];
+                    for (int e = 0; e < 4; ++e) oc[x][d][e] *= alpha;
+                m[x] = mn;
             }
-        l += acc;
+            if constexpr (MODE == SA_CAUSAL) {   // raw scores: one packed FMA per pair, then exp2
+                const fa_f32x2 sc2 = {scale_log2, scale_log2}, nm2 = {-mn, -mn};
+                fa_f32x2 acc2 = {0.f, 0.f};
+#pragma unroll
+                for (int f = 0; f < KF; ++f)
+#pragma unroll
+                    for (int e = 0; e < 4; e += 2) {
+                        fa_f32x2 t = (fa_f32x2){sf[x][f][e], sf[x][f][e + 1]} * sc2 + nm2;
+                        t.x = __builtin_amdgcn_exp2f(t.x);
+                        t.y = __builtin_amdgcn_exp2f(t.y);
+                        sf[x][f][e] = t.x;
+                        sf[x][f][e + 1] = t.y;
+                        acc2 = acc2 + t;
+                    }
+                l[x] += acc2.x + acc2.y;
+            } else {
+                float acc = 0.f;
+#pragma unroll
+                for (int f = 0; f < KF; ++f)
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        sf[x][f][e] = __builtin_amdgcn_exp2f(sf[x][f][e] - mn);
+                        acc += sf[x][f][e];
+                    }
+                l[x] += acc;
+            }
+        }
 #pragma unroll
         for (int j = 0; j < KF / 2; ++j) {
-            la_bf16x8 bp;
+            la_bf16x8 bp[QF];
 #pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                bp[e] = (__bf16)sf[2 * j][e];
-                bp[4 + e] = (__bf16)sf[2 * j + 1][e];
-            }
+            for (int x = 0; x < QF; ++x)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    bp[x][e] = (__bf16)sf[x][2 * j][e];
+                    bp[x][4 + e] = (__bf16)sf[x][2 * j + 1][e];
+                }
 #pragma unroll
             for (int d = 0; d < DF; ++d) {
-                const la_bf16x8 av = xa_tr8_perm<RB_RS>(sv + (32 * j) * RB_RS + 16 * d, lane);
-                oc[d] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av, bp, oc[d], 0, 0, 0);
+                const la_bf16x8 av = xa_tr8_perm<RS>(sv + (32 * j) * RS + 16 * d, lane);
+#pragma unroll
+                for (int x = 0; x < QF; ++x) oc[x][d] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av, bp[x], oc[x][d], 0, 0, 0);
             }
         }
     }
-    const float sum = g4_sum(l);
-    if (qr < N) {
-        const bool valid = qr < L;
-        const float inv = 1.0f / sum;
-        unsigned short* dst = o + (row0 + qr) * ldo + (int64_t)h * RB_HD + 4 * g;
 #pragma unroll
-        for (int d = 0; d < DF; ++d) {
-            u16x4m t;
+    for (int x = 0; x < QF; ++x) {
+        const float sum = g4_sum(l[x]);
+        const int qr = q0 + 16 * x + r16;
+        if (qr < N) {
+            const bool valid = qr < L;
+            const float inv = 1.0f / sum;
+            unsigned short* dst = o + (row0 + qr) * ldo + (int64_t)h * HD + 4 * g;
 #pragma unroll
-            for (int e = 0; e < 4; ++e) t[e] = valid ? f2b(oc[d][e] * inv) : (unsigned short)0;
-            *reinterpret_cast<u16x4m*>(dst + 16 * d) = t;
+            for (int d = 0; d < DF; ++d) {
+                u16x4m t;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) t[e] = valid ? f2b(oc[x][d][e] * inv) : (unsigned short)0;
+                *reinterpret_cast<u16x4m*>(dst + 16 * d) = t;
+            }
         }
     }
+}
+
+// The argument checks the three entry points share; `fn` names the entry point in every message.  nmax: the
+// largest N the instance takes; qblk: its query block.  An empty batch (B == 0) is accepted before any pointer
+// is looked at and gives *nqb = 0: nothing to launch.
+static int seq_attn_args(const char* fn, int hd, int qblk, int64_t nmax, const void* q, int64_t ldq, const void* k,
+                         int64_t ldk, const void* v, int64_t ldv, const int32_t* lens, int64_t B, int64_t heads_q,
+                         int64_t heads_kv, int64_t N, int64_t head_dim, const void* o, int64_t ldo, int64_t* nqb) {
+    *nqb = 0;
+    EGG_CHECK_ARG(head_dim == hd, "%s: head_dim %lld unsupported (%d)", fn, (long long)head_dim, hd);
+    EGG_CHECK_ARG(B >= 0 && heads_kv >= 1 && heads_q >= heads_kv && heads_q % heads_kv == 0,
+                  "%s: bad sizes B=%lld heads_q=%lld heads_kv=%lld (heads_q = G * heads_kv)", fn, (long long)B,
+                  (long long)heads_q, (long long)heads_kv);
+    if (B == 0) return EGGROLL_OK;
+    EGG_CHECK_ARG(N >= 1 && N <= nmax, "%s: N=%lld outside [1, %lld]", fn, (long long)N, (long long)nmax);
+    EGG_CHECK_ARG(ldq % 8 == 0 && ldk % 8 == 0 && ldv % 8 == 0 && ldo % 4 == 0 && ldq >= heads_q * hd &&
+                  ldk >= heads_kv * hd && ldv >= heads_kv * hd && ldo >= heads_q * hd, "%s: bad strides", fn);
+    EGG_CHECK_ARG(q && k && v && o && lens, "%s: NULL pointer", fn);
+    EGG_CHECK_ARG(((uintptr_t)q & 15) == 0 && ((uintptr_t)k & 15) == 0 && ((uintptr_t)v & 15) == 0 && ((uintptr_t)o & 7) == 0 &&
+                  ((uintptr_t)lens & 3) == 0, "%s: q/k/v must be 16-byte aligned, o 8-byte aligned", fn);
+    const int64_t n = (N + qblk - 1) / qblk;
+    EGG_CHECK_ARG(B * heads_q * n < (1ll << 31), "%s: grid too large", fn);
+    *nqb = n;
+    return EGGROLL_OK;
+}
+
+template <int MODE, int HD, int KB, int QF, int RS, int MINB>
+static int seq_attn_launch(const char* fn, const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v,
+                           int64_t ldv, const float* rel_bias, int64_t R, const int32_t* lens, int64_t B,
+                           int64_t heads_q, int64_t heads_kv, int64_t N, int64_t nqb, float scale, float cap, void* o,
+                           int64_t ldo, void* stream) {
+    const float LOG2E = 1.4426950408889634f;
+    hipLaunchKernelGGL((k_seq_attn<MODE, HD, KB, QF, RS, MINB>), dim3((unsigned)(B * heads_q * nqb)), dim3(256), 0,
+                       as_stream(stream), (const unsigned short*)q, ldq, (const unsigned short*)k, ldk,
+                       (const unsigned short*)v, ldv, rel_bias, (int)R, lens, (int)heads_q, (int)(heads_q / heads_kv),
+                       (int)N, (int)nqb, scale * LOG2E, cap > 0.0f ? 2.0f * LOG2E * scale / cap : 0.0f, cap * LOG2E,
+                       (unsigned short*)o, ldo);
+    EGG_CHECK_LAUNCH(fn);
+    return EGGROLL_OK;
 }
 
 extern "C" int eggroll_relbias_attention(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v,
                                          int64_t ldv, const float* rel_bias, int64_t R, const int32_t* lens, int64_t B,
                                          int64_t heads, int64_t N, int64_t head_dim, float scale, void* o, int64_t ldo,
                                          void* stream) {
-    EGG_CHECK_ARG(head_dim == RB_HD, "relbias_attention: head_dim %lld unsupported (64)", (long long)head_dim);
-    EGG_CHECK_ARG(B >= 0 && heads >= 1, "relbias_attention: bad sizes B=%lld heads=%lld", (long long)B, (long long)heads);
-    if (B == 0) return EGGROLL_OK;
-    EGG_CHECK_ARG(N >= 1 && N <= RB_NMAX, "relbias_attention: N=%lld outside [1, %d]", (long long)N, RB_NMAX);
-    EGG_CHECK_ARG(R >= N && R < (1ll << 24), "relbias_attention: rel_bias is [heads][2R-1] with R >= N (R=%lld, N=%lld)",
+    const char* fn = "relbias_attention";
+    int64_t nqb;
+    if (int rc = seq_attn_args(fn, 64, 64, RB_NMAX, q, ldq, k, ldk, v, ldv, lens, B, heads, heads, N, head_dim, o, ldo, &nqb))
+        return rc;
+    if (nqb == 0) return EGGROLL_OK;
+    EGG_CHECK_ARG(R >= N && R < (1ll << 24), "%s: rel_bias is [heads][2R-1] with R >= N (R=%lld, N=%lld)", fn,
                   (long long)R, (long long)N);
-    EGG_CHECK_ARG(ldq % 8 == 0 && ldk % 8 == 0 && ldv % 8 == 0 && ldo % 4 == 0 && ldq >= heads * RB_HD &&
-                  ldk >= heads * RB_HD && ldv >= heads * RB_HD && ldo >= heads * RB_HD, "relbias_attention: bad strides");
-    EGG_CHECK_ARG(q && k && v && o && rel_bias && lens, "relbias_attention: NULL pointer");
-    EGG_CHECK_ARG(((uintptr_t)q & 15) == 0 && ((uintptr_t)k & 15) == 0 && ((uintptr_t)v & 15) == 0 && ((uintptr_t)o & 7) == 0 &&
-                  ((uintptr_t)rel_bias & 3) == 0 && ((uintptr_t)lens & 3) == 0,
-                  "relbias_attention: q/k/v must be 16-byte aligned, o 8-byte aligned");
-    const int64_t nqb = (N + RB_QB - 1) / RB_QB;
-    EGG_CHECK_ARG(B * heads * nqb < (1ll << 31), "relbias_attention: grid too large");
-    hipLaunchKernelGGL(k_relbias_attn, dim3((unsigned)(B * heads * nqb)), dim3(256), 0, as_stream(stream),
-                       (const unsigned short*)q, ldq, (const unsigned short*)k, ldk, (const unsigned short*)v, ldv,
-                       rel_bias, (int)R, lens, (int)heads, (int)N, (int)nqb, scale * 1.4426950408889634f,
-                       (unsigned short*)o, ldo);
-    EGG_CHECK_LAUNCH("relbias_attention");
-    return EGGROLL_OK;
-}
-
-// ------------------------------------------------------------------------------------
-// Causal attention with a tanh soft-cap on the logits, grouped KV heads and per-sequence key lengths, head
-// dim 256 (the Gemma-2 prompt encoder of Sana):
-//   o[b, i, h, :] = softmax_{j <= i, j < len[b]}(cap > 0 ? cap * tanh(scale * q[b,i,h,:] . k[b,j,h/G,:] / cap)
-//                                                        : scale * q . k) @ v[b, j, h/G, :],  G = heads_q / heads_kv
-// q / k / v / o: rows b*N + i of bf16 matrices with their own row strides, head h at columns 256 h (the
-// output of one fused qkv GEMM is read in place).  k_relbias_attn's scheme at head dim 256: workgroup =
-// (b, query head, 64-query block), 4 waves x 16 queries, S^T = K Q^T so each lane holds 4 keys of ONE query,
-// online softmax in the exp2 domain, the next key block held in registers.  Keys come in blocks of 32: per
-// lane 32 VGPRs of Q fragments, 64 of output accumulators, 32 of prefetch; k + v of a block are
-// 2 x 32 x 264 x 2 B = 33 KB of LDS.  No table over N lives in LDS, so N has no upper limit.  A query block
-// sweeps the key blocks up to its own last query (and below len[b]); a wave skips the arithmetic of a block
-// that lies wholly past its 16 queries (the barriers stay block-uniform); blocks that reach past the wave's
-// first query or past len[b] take -inf where key > query or key >= len[b].  Key 0 is visible to every
-// query of a swept block, so the running max is finite after the first block.  The soft-cap is evaluated in
-// fp32 before the mask as tanh(x) = 1 - 2 / (exp2(2 x log2 e) + 1), which saturates to +-1 without a NaN.
-// Key rows are read clamped to len[b] - 1; query rows >= len[b] are written as zeros.
-// ------------------------------------------------------------------------------------
-constexpr int SC_HD = 256, SC_KB = 32, SC_QB = 64, SC_RS = SC_HD + 8;
-
-__global__ __launch_bounds__(256) void k_softcap_attn(const unsigned short* __restrict__ q, int64_t ldq,
-                                                      const unsigned short* __restrict__ k, int64_t ldk,
-                                                      const unsigned short* __restrict__ v, int64_t ldv,
-                                                      const int* __restrict__ lens, int heads_q, int group, int N,
-                                                      int nqb, float scale_log2, float cap_in, float cap_log2,
-                                                      unsigned short* __restrict__ o, int64_t ldo) {
-    constexpr int KSN = SC_HD / 32, DF = SC_HD / 16, KF = SC_KB / 16, CH = SC_HD / 8;
-    constexpr int UNITS = 2 * SC_KB * CH / 256;   // 16-B chunks of k + v per thread per key block (8)
-    __shared__ __attribute__((aligned(16))) unsigned short sk[SC_KB * SC_RS];
-    __shared__ __attribute__((aligned(16))) unsigned short sv[SC_KB * SC_RS];
-    const int bid = xcd_remap(blockIdx.x, gridDim.x);
-    const int qb = bid % nqb, bh = bid / nqb;
-    const int b = bh / heads_q, h = bh - b * heads_q, hk = h / group;
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, r16 = lane & 15, g = lane >> 4;
-    const int L = min(max(lens[b], 0), N);
-    const int64_t row0 = (int64_t)b * N;
-    if (qb * SC_QB >= L) {   // no valid query in this block (block-uniform): zeros, before any barrier
-#pragma unroll
-        for (int i = 0; i < SC_QB * (SC_HD / 4) / 256; ++i) {
-            const int c = tid + 256 * i, r = c / (SC_HD / 4), cc = c - r * (SC_HD / 4);
-            if (qb * SC_QB + r < N)
-                *reinterpret_cast<u16x4m*>(o + (row0 + qb * SC_QB + r) * ldo + (int64_t)h * SC_HD + 4 * cc) =
-                    u16x4m{0, 0, 0, 0};
-        }
-        return;
-    }
-    const unsigned short* kb_ = k + row0 * ldk + (int64_t)hk * SC_HD;
-    const unsigned short* vb_ = v + row0 * ldv + (int64_t)hk * SC_HD;
-    // Q^T fragments (B operand): dims 32 ks + 8 g .. +7 of query r16 of this wave's 16
-    const int qw0 = qb * SC_QB + w * 16, qr = qw0 + r16;
-    la_bf16x8 bq[KSN];
-#pragma unroll
-    for (int ks = 0; ks < KSN; ++ks) {
-        u16x8m t = u16x8m{0, 0, 0, 0, 0, 0, 0, 0};
-        if (qr < N) t = *reinterpret_cast<const u16x8m*>(q + (row0 + qr) * ldq + (int64_t)h * SC_HD + 32 * ks + 8 * g);
-        bq[ks] = __builtin_bit_cast(la_bf16x8, t);
-    }
-    u16x8m pre[UNITS];
-    auto load_blk = [&](int key0) {
-#pragma unroll
-        for (int i = 0; i < UNITS; ++i) {
-            const int c = tid + 256 * i;             // [k | v][row][chunk]
-            const int kv = c / (SC_KB * CH), rc = c - kv * (SC_KB * CH);
-            const int r = rc / CH, cc = rc - r * CH;
-            // branch-free: rows past L read the last valid key (in bounds) and are zeroed by a select
-            const int row = min(key0 + r, L - 1);
-            const unsigned short* src = kv ? vb_ + (int64_t)row * ldv : kb_ + (int64_t)row * ldk;
-            const u16x8m t = *reinterpret_cast<const u16x8m*>(src + cc * 8);
-            pre[i] = key0 + r < L ? t : u16x8m{0, 0, 0, 0, 0, 0, 0, 0};
-        }
-    };
-    auto store_blk = [&]() {
-#pragma unroll
-        for (int i = 0; i < UNITS; ++i) {
-            const int c = tid + 256 * i;
-            const int kv = c / (SC_KB * CH), rc = c - kv * (SC_KB * CH);
-            const int r = rc / CH, cc = rc - r * CH;
-            *reinterpret_cast<u16x8m*>((kv ? sv : sk) + r * SC_RS + cc * 8) = pre[i];
-        }
-    };
-    la_f32x4 oc[DF];
-#pragma unroll
-    for (int d = 0; d < DF; ++d) oc[d] = la_f32x4{0.f, 0.f, 0.f, 0.f};
-    float m = -INFINITY, l = 0.0f;
-    const int kend = min(L, qb * SC_QB + SC_QB);   // keys [0, kend): causal for the block's last query, below len
-    const int nkb = (kend + SC_KB - 1) / SC_KB;
-    load_blk(0);
-    for (int kb = 0; kb < nkb; ++kb) {
-        __syncthreads();   // every wave is done reading the previous block
-        store_blk();
-        __syncthreads();
-        if (kb + 1 < nkb) load_blk((kb + 1) * SC_KB);   // in flight under this block's MFMAs
-        const int key0 = kb * SC_KB;
-        if (key0 > qw0 + 15) continue;   // wholly past this wave's queries (wave-uniform; barriers are above)
-        la_f32x4 sf[KF];
-#pragma unroll
-        for (int ks = 0; ks < KSN; ++ks) {
-#pragma unroll
-            for (int f = 0; f < KF; ++f) {
-                const la_bf16x8 a = *reinterpret_cast<const la_bf16x8*>(sk + (16 * f + r16) * SC_RS + 32 * ks + 8 * g);
-                sf[f] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, bq[ks], ks ? sf[f] : la_f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
-            }
-        }
-        // t = log2 e * softcap(scale * s); lane: keys key0 + 16 f + 4 g + e of query qr
-        if (cap_log2 > 0.0f) {   // cap_in = 2 log2 e * scale / cap, cap_log2 = log2 e * cap
-#pragma unroll
-            for (int f = 0; f < KF; ++f)
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const float ex = __builtin_amdgcn_exp2f(sf[f][e] * cap_in);   // +inf / 0 at the ends: tanh = +-1
-                    sf[f][e] = fmaf(-2.0f * cap_log2, __builtin_amdgcn_rcpf(ex + 1.0f), cap_log2);
-                }
-        } else {
-#pragma unroll
-            for (int f = 0; f < KF; ++f)
-#pragma unroll
-                for (int e = 0; e < 4; ++e) sf[f][e] *= scale_log2;
-        }
-        if (key0 + SC_KB > L || key0 + SC_KB - 1 > qw0) {   // the diagonal / the partial last block (wave-uniform)
-#pragma unroll
-            for (int f = 0; f < KF; ++f)
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const int key = key0 + 16 * f + 4 * g + e;
-                    sf[f][e] = (key < L && key <= qr) ? sf[f][e] : -INFINITY;
-                }
-        }
-        float mb = fmaxf(fmaxf(sf[0][0], sf[0][1]), fmaxf(sf[0][2], sf[0][3]));
-#pragma unroll
-        for (int f = 1; f < KF; ++f) mb = fmaxf(fmaxf(mb, fmaxf(sf[f][0], sf[f][1])), fmaxf(sf[f][2], sf[f][3]));
-        mb = g4_max(mb);   // -inf only in a later block with no visible key: then mn = m, finite since block 0
-        const float mn = fmaxf(m, mb);
-        if (__builtin_amdgcn_ballot_w64(mn != m)) {   // a running max moved: rescale
-            const float alpha = __builtin_amdgcn_exp2f(m - mn);   // 0 on the first block (m = -inf)
-            l *= alpha;
-#pragma unroll
-            for (int d = 0; d < DF; ++d)
-#pragma unroll
-                for (int e = 0; e < 4; ++e) oc[d][e] *= alpha;
-            m = mn;
-        }
-        float acc = 0.f;
-#pragma unroll
-        for (int f = 0; f < KF; ++f)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                sf[f][e] = __builtin_amdgcn_exp2f(sf[f][e] - mn);
-                acc += sf[f][e];
-            }
-        l += acc;
-#pragma unroll
-        for (int j = 0; j < KF / 2; ++j) {
-            la_bf16x8 bp;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                bp[e] = (__bf16)sf[2 * j][e];
-                bp[4 + e] = (__bf16)sf[2 * j + 1][e];
-            }
-#pragma unroll
-            for (int d = 0; d < DF; ++d) {
-                const la_bf16x8 av = xa_tr8_perm<SC_RS>(sv + (32 * j) * SC_RS + 16 * d, lane);
-                oc[d] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av, bp, oc[d], 0, 0, 0);
-            }
-        }
-    }
-    const float sum = g4_sum(l);
-    if (qr < N) {
-        const bool valid = qr < L;
-        const float inv = 1.0f / sum;
-        unsigned short* dst = o + (row0 + qr) * ldo + (int64_t)h * SC_HD + 4 * g;
-#pragma unroll
-        for (int d = 0; d < DF; ++d) {
-            u16x4m t;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) t[e] = valid ? f2b(oc[d][e] * inv) : (unsigned short)0;
-            *reinterpret_cast<u16x4m*>(dst + 16 * d) = t;
-        }
-    }
+    EGG_CHECK_ARG(rel_bias && ((uintptr_t)rel_bias & 3) == 0, "%s: rel_bias is NULL or not 4-byte aligned", fn);
+    return seq_attn_launch<SA_RELBIAS, 64, 64, 1, 72, 1>(fn, q, ldq, k, ldk, v, ldv, rel_bias, R, lens, B, heads, heads, N,
+                                                         nqb, scale, 0.0f, o, ldo, stream);
 }
 
 extern "C" int eggroll_softcap_attention(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v,
                                          int64_t ldv, const int32_t* lens, int64_t B, int64_t heads_q, int64_t heads_kv,
                                          int64_t N, int64_t head_dim, float scale, float cap, void* o, int64_t ldo,
                                          void* stream) {
-    EGG_CHECK_ARG(head_dim == SC_HD, "softcap_attention: head_dim %lld unsupported (256)", (long long)head_dim);
-    EGG_CHECK_ARG(B >= 0 && heads_kv >= 1 && heads_q >= heads_kv && heads_q % heads_kv == 0,
-                  "softcap_attention: bad sizes B=%lld heads_q=%lld heads_kv=%lld (heads_q = G * heads_kv)", (long long)B,
-                  (long long)heads_q, (long long)heads_kv);
-    EGG_CHECK_ARG(cap >= 0.0f && cap < INFINITY, "softcap_attention: cap must be finite and >= 0 (0: no soft-cap)");
-    if (B == 0) return EGGROLL_OK;
-    EGG_CHECK_ARG(N >= 1 && N < (1ll << 31) - SC_QB, "softcap_attention: N=%lld outside [1, 2^31 - 64)", (long long)N);
-    EGG_CHECK_ARG(ldq % 8 == 0 && ldk % 8 == 0 && ldv % 8 == 0 && ldo % 4 == 0 && ldq >= heads_q * SC_HD &&
-                  ldk >= heads_kv * SC_HD && ldv >= heads_kv * SC_HD && ldo >= heads_q * SC_HD,
-                  "softcap_attention: bad strides");
-    EGG_CHECK_ARG(q && k && v && o && lens, "softcap_attention: NULL pointer");
-    EGG_CHECK_ARG(((uintptr_t)q & 15) == 0 && ((uintptr_t)k & 15) == 0 && ((uintptr_t)v & 15) == 0 && ((uintptr_t)o & 7) == 0 &&
-                  ((uintptr_t)lens & 3) == 0, "softcap_attention: q/k/v must be 16-byte aligned, o 8-byte aligned");
-    const int64_t nqb = (N + SC_QB - 1) / SC_QB;
-    EGG_CHECK_ARG(B * heads_q * nqb < (1ll << 31), "softcap_attention: grid too large");
-    const float LOG2E = 1.4426950408889634f;
-    hipLaunchKernelGGL(k_softcap_attn, dim3((unsigned)(B * heads_q * nqb)), dim3(256), 0, as_stream(stream),
-                       (const unsigned short*)q, ldq, (const unsigned short*)k, ldk, (const unsigned short*)v, ldv, lens,
-                       (int)heads_q, (int)(heads_q / heads_kv), (int)N, (int)nqb, scale * LOG2E,
-                       cap > 0.0f ? 2.0f * LOG2E * scale / cap : 0.0f, cap * LOG2E, (unsigned short*)o, ldo);
-    EGG_CHECK_LAUNCH("softcap_attention");
-    return EGGROLL_OK;
+    const char* fn = "softcap_attention";
+    EGG_CHECK_ARG(cap >= 0.0f && cap < INFINITY, "%s: cap must be finite and >= 0 (0: no soft-cap)", fn);
+    int64_t nqb;
+    if (int rc = seq_attn_args(fn, 256, 64, (1ll << 31) - 64 - 1, q, ldq, k, ldk, v, ldv, lens, B, heads_q, heads_kv, N,
+                               head_dim, o, ldo, &nqb))
+        return rc;
+    if (nqb == 0) return EGGROLL_OK;
+    return seq_attn_launch<SA_SOFTCAP, 256, 32, 1, 264, 1>(fn, q, ldq, k, ldk, v, ldv, nullptr, 0, lens, B, heads_q,
+                                                           heads_kv, N, nqb, scale, cap, o, ldo, stream);
+}
+
+extern "C" int eggroll_causal_attention(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v,
+                                        int64_t ldv, const int32_t* lens, int64_t B, int64_t heads_q, int64_t heads_kv,
+                                        int64_t N, int64_t head_dim, float scale, void* o, int64_t ldo, void* stream) {
+    const char* fn = "causal_attention";
+    EGG_CHECK_ARG(scale > 0.0f && scale < INFINITY, "%s: scale must be finite and > 0", fn);
+    int64_t nqb;
+    if (int rc = seq_attn_args(fn, FA_HD, 128, (1ll << 31) - 128 - 1, q, ldq, k, ldk, v, ldv, lens, B, heads_q, heads_kv, N,
+                               head_dim, o, ldo, &nqb))
+        return rc;
+    if (nqb == 0) return EGGROLL_OK;
+    return seq_attn_launch<SA_CAUSAL, FA_HD, FA_KB, 2, FA_RS, 2>(fn, q, ldq, k, ldk, v, ldv, nullptr, 0, lens, B, heads_q,
+                                                                 heads_kv, N, nqb, scale, 0.0f, o, ldo, stream);
 }
 
 // ------------------------------------------------------------------------------------
@@ -3072,227 +3028,6 @@ extern "C" int eggroll_rope_half(void* x, int64_t ldx, int64_t B, int64_t N, int
     hipLaunchKernelGGL(k_rope_half, dim3((unsigned)nblk), dim3(256), 0, as_stream(stream), (unsigned short*)x, ldx, B * N,
                        (int)N, (int)heads, cos_t, sin_t);
     EGG_CHECK_LAUNCH("rope_half");
-    return EGGROLL_OK;
-}
-
-// ------------------------------------------------------------------------------------
-// Causal attention with grouped KV heads and per-sequence key lengths, head dim 128 (the Qwen3 prompt
-// encoder of Z-Image):
-//   o[b, i, h, :] = softmax_{j <= i, j < len[b]}(scale * q[b,i,h,:] . k[b,j,h/G,:]) @ v[b, j, h/G, :],  G = heads_q / heads_kv
-// q / k / v / o: rows b*N + i of bf16 matrices with their own row strides, head h at columns 128 h (the
-// output of one fused qkv GEMM is read in place).  k_flash_attn<2>'s scheme with k_softcap_attn's masks:
-// workgroup = (b, query head, 128-query block), 4 waves x 32 queries (two sets of 16), 64-key blocks of
-// KV head h / G in LDS at row stride 144, the next block held in registers, S^T = K Q^T so each lane holds
-// 4 keys of ONE query, online softmax in base 2 on raw scores, P rounded to bf16, V^T through
-// ds_read_tr16_b64.  The G workgroups of one KV head have adjacent ids under xcd_remap, so their K / V reads
-// meet in one XCD's L2.  A query block sweeps the key blocks that hold a key < min(len[b], its last query +
-// 1); a wave skips the arithmetic of a block wholly past its 32 queries (the barriers stay block-uniform);
-// the j <= i / j < len selects run only in blocks that reach past the wave's first query or past len[b]
-// (wave-uniform branch).  Block 0 is swept first and holds key 0, visible to every query, so a running max
-// is finite before any all-masked block is met: exp2(m - mn) never sees -inf - -inf.  Key rows are read
-// clamped to len[b] - 1; query rows >= len[b] are written as zeros.
-// ------------------------------------------------------------------------------------
-constexpr int CA_QF = 2, CA_QW = 16 * CA_QF, CA_QB = 4 * CA_QW;
-
-__global__ __launch_bounds__(256, 2) void k_causal_attn(const unsigned short* __restrict__ q, int64_t ldq,
-                                                        const unsigned short* __restrict__ k, int64_t ldk,
-                                                        const unsigned short* __restrict__ v, int64_t ldv,
-                                                        const int* __restrict__ lens, int heads_q, int group, int N,
-                                                        int nqb, float scale_log2, unsigned short* __restrict__ o,
-                                                        int64_t ldo) {
-    constexpr int QF = CA_QF, KSN = FA_HD / 32, DF = FA_HD / 16, KF = FA_KB / 16, CH = FA_HD / 8;
-    constexpr int UNITS = 2 * FA_KB * CH / 256;   // 16-B chunks of k + v per thread per key block (8)
-    __shared__ __attribute__((aligned(16))) unsigned short sk[FA_KB * FA_RS];
-    __shared__ __attribute__((aligned(16))) unsigned short sv[FA_KB * FA_RS];
-    const int bid = xcd_remap(blockIdx.x, gridDim.x);
-    const int qb = bid % nqb, bh = bid / nqb;
-    const int b = bh / heads_q, h = bh - b * heads_q, hk = h / group;
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, r16 = lane & 15, g = lane >> 4;
-    const int L = min(max(lens[b], 0), N);
-    const int64_t row0 = (int64_t)b * N;
-    if (qb * CA_QB >= L) {   // no valid query in this block (block-uniform): zeros, before any barrier
-#pragma unroll
-        for (int i = 0; i < CA_QB * (FA_HD / 4) / 256; ++i) {
-            const int c = tid + 256 * i, r = c / (FA_HD / 4), cc = c - r * (FA_HD / 4);
-            if (qb * CA_QB + r < N)
-                *reinterpret_cast<u16x4m*>(o + (row0 + qb * CA_QB + r) * ldo + (int64_t)h * FA_HD + 4 * cc) =
-                    u16x4m{0, 0, 0, 0};
-        }
-        return;
-    }
-    const unsigned short* kb_ = k + row0 * ldk + (int64_t)hk * FA_HD;
-    const unsigned short* vb_ = v + row0 * ldv + (int64_t)hk * FA_HD;
-    // Q^T fragments (B operand): dims 32 ks + 8 g .. +7 of query 16 x + r16 of this wave's 32
-    const int q0 = qb * CA_QB + w * CA_QW;
-    la_bf16x8 bq[QF][KSN];
-#pragma unroll
-    for (int x = 0; x < QF; ++x) {
-        const int qr = q0 + 16 * x + r16;
-#pragma unroll
-        for (int ks = 0; ks < KSN; ++ks) {
-            u16x8m t = u16x8m{0, 0, 0, 0, 0, 0, 0, 0};
-            if (qr < N) t = *reinterpret_cast<const u16x8m*>(q + (row0 + qr) * ldq + (int64_t)h * FA_HD + 32 * ks + 8 * g);
-            bq[x][ks] = __builtin_bit_cast(la_bf16x8, t);
-        }
-    }
-    u16x8m pre[UNITS];
-    auto load_blk = [&](int key0) {
-#pragma unroll
-        for (int i = 0; i < UNITS; ++i) {
-            const int c = tid + 256 * i;             // [k | v][row][chunk]
-            const int kv = c / (FA_KB * CH), rc = c - kv * (FA_KB * CH);
-            const int r = rc / CH, cc = rc - r * CH;
-            // branch-free: rows past L read the last valid key (in bounds) and are zeroed by a select
-            const int row = min(key0 + r, L - 1);
-            const unsigned short* src = kv ? vb_ + (int64_t)row * ldv : kb_ + (int64_t)row * ldk;
-            const u16x8m t = *reinterpret_cast<const u16x8m*>(src + cc * 8);
-            pre[i] = key0 + r < L ? t : u16x8m{0, 0, 0, 0, 0, 0, 0, 0};
-        }
-    };
-    auto store_blk = [&]() {
-#pragma unroll
-        for (int i = 0; i < UNITS; ++i) {
-            const int c = tid + 256 * i;
-            const int kv = c / (FA_KB * CH), rc = c - kv * (FA_KB * CH);
-            const int r = rc / CH, cc = rc - r * CH;
-            *reinterpret_cast<u16x8m*>((kv ? sv : sk) + r * FA_RS + cc * 8) = pre[i];
-        }
-    };
-    la_f32x4 oc[QF][DF];
-    float m[QF], l[QF];
-#pragma unroll
-    for (int x = 0; x < QF; ++x) {
-        m[x] = -INFINITY;
-        l[x] = 0.0f;
-#pragma unroll
-        for (int d = 0; d < DF; ++d) oc[x][d] = la_f32x4{0.f, 0.f, 0.f, 0.f};
-    }
-    const int kend = min(L, qb * CA_QB + CA_QB);   // keys [0, kend): causal for the block's last query, below len
-    const int nkb = (kend + FA_KB - 1) / FA_KB;
-    load_blk(0);
-    for (int kb = 0; kb < nkb; ++kb) {
-        __syncthreads();   // every wave is done reading the previous block
-        store_blk();
-        __syncthreads();
-        if (kb + 1 < nkb) load_blk((kb + 1) * FA_KB);   // in flight under this block's MFMAs
-        const int key0 = kb * FA_KB;
-        if (key0 > q0 + CA_QW - 1) continue;   // wholly past this wave's queries (wave-uniform; barriers are above)
-        la_f32x4 sf[QF][KF];
-#pragma unroll
-        for (int ks = 0; ks < KSN; ++ks) {
-#pragma unroll
-            for (int f = 0; f < KF; ++f) {
-                const la_bf16x8 a = *reinterpret_cast<const la_bf16x8*>(sk + (16 * f + r16) * FA_RS + 32 * ks + 8 * g);
-#pragma unroll
-                for (int x = 0; x < QF; ++x)
-                    sf[x][f] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, bq[x][ks], ks ? sf[x][f] : la_f32x4{0.f, 0.f, 0.f, 0.f},
-                                                                       0, 0, 0);
-            }
-        }
-        // lane: keys key0 + 16 f + 4 g + e of query q0 + 16 x + r16
-        if (key0 + FA_KB > L || key0 + FA_KB - 1 > q0) {   // the diagonal / the partial last block (wave-uniform)
-#pragma unroll
-            for (int f = 0; f < KF; ++f)
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const int key = key0 + 16 * f + 4 * g + e;
-#pragma unroll
-                    for (int x = 0; x < QF; ++x)
-                        sf[x][f][e] = (key < L && key <= q0 + 16 * x + r16) ? sf[x][f][e] : -INFINITY;
-                }
-        }
-#pragma unroll
-        for (int x = 0; x < QF; ++x) {
-            float mb = fmaxf(fmaxf(sf[x][0][0], sf[x][0][1]), fmaxf(sf[x][0][2], sf[x][0][3]));
-#pragma unroll
-            for (int f = 1; f < KF; ++f)
-                mb = fmaxf(fmaxf(mb, fmaxf(sf[x][f][0], sf[x][f][1])), fmaxf(sf[x][f][2], sf[x][f][3]));
-            mb = g4_max(mb);   // -inf only in a later block with no visible key: then mn = m, finite since block 0
-            const float mn = fmaxf(m[x], mb * scale_log2);   // scale > 0 commutes with max
-            if (__builtin_amdgcn_ballot_w64(mn != m[x])) {   // a running max moved: rescale this query set
-                const float alpha = __builtin_amdgcn_exp2f(m[x] - mn);   // 0 on the first block (m = -inf)
-                l[x] *= alpha;
-#pragma unroll
-                for (int d = 0; d < DF; ++d)
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) oc[x][d][e] *= alpha;
-                m[x] = mn;
-            }
-            const fa_f32x2 sc2 = {scale_log2, scale_log2}, nm2 = {-mn, -mn};
-            fa_f32x2 acc2 = {0.f, 0.f};
-#pragma unroll
-            for (int f = 0; f < KF; ++f)
-#pragma unroll
-                for (int e = 0; e < 4; e += 2) {
-                    fa_f32x2 t = (fa_f32x2){sf[x][f][e], sf[x][f][e + 1]} * sc2 + nm2;
-                    t.x = __builtin_amdgcn_exp2f(t.x);
-                    t.y = __builtin_amdgcn_exp2f(t.y);
-                    sf[x][f][e] = t.x;
-                    sf[x][f][e + 1] = t.y;
-                    acc2 = acc2 + t;
-                }
-            l[x] += acc2.x + acc2.y;
-        }
-#pragma unroll
-        for (int j = 0; j < KF / 2; ++j) {
-            la_bf16x8 bp[QF];
-#pragma unroll
-            for (int x = 0; x < QF; ++x)
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    bp[x][e] = (__bf16)sf[x][2 * j][e];
-                    bp[x][4 + e] = (__bf16)sf[x][2 * j + 1][e];
-                }
-#pragma unroll
-            for (int d = 0; d < DF; ++d) {
-                const la_bf16x8 av = xa_tr8_perm<FA_RS>(sv + (32 * j) * FA_RS + 16 * d, lane);
-#pragma unroll
-                for (int x = 0; x < QF; ++x) oc[x][d] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av, bp[x], oc[x][d], 0, 0, 0);
-            }
-        }
-    }
-#pragma unroll
-    for (int x = 0; x < QF; ++x) {
-        const float sum = g4_sum(l[x]);
-        const int qr = q0 + 16 * x + r16;
-        if (qr < N) {
-            const bool valid = qr < L;
-            const float inv = 1.0f / sum;
-            unsigned short* dst = o + (row0 + qr) * ldo + (int64_t)h * FA_HD + 4 * g;
-#pragma unroll
-            for (int d = 0; d < DF; ++d) {
-                u16x4m t;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) t[e] = valid ? f2b(oc[x][d][e] * inv) : (unsigned short)0;
-                *reinterpret_cast<u16x4m*>(dst + 16 * d) = t;
-            }
-        }
-    }
-}
-
-extern "C" int eggroll_causal_attention(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v,
-                                        int64_t ldv, const int32_t* lens, int64_t B, int64_t heads_q, int64_t heads_kv,
-                                        int64_t N, int64_t head_dim, float scale, void* o, int64_t ldo, void* stream) {
-    EGG_CHECK_ARG(head_dim == FA_HD, "causal_attention: head_dim %lld unsupported (128)", (long long)head_dim);
-    EGG_CHECK_ARG(B >= 0 && heads_kv >= 1 && heads_q >= heads_kv && heads_q % heads_kv == 0,
-                  "causal_attention: bad sizes B=%lld heads_q=%lld heads_kv=%lld (heads_q = G * heads_kv)", (long long)B,
-                  (long long)heads_q, (long long)heads_kv);
-    EGG_CHECK_ARG(scale > 0.0f && scale < INFINITY, "causal_attention: scale must be finite and > 0");
-    if (B == 0) return EGGROLL_OK;
-    EGG_CHECK_ARG(N >= 1 && N < (1ll << 31) - CA_QB, "causal_attention: N=%lld outside [1, 2^31 - 128)", (long long)N);
-    EGG_CHECK_ARG(ldq % 8 == 0 && ldk % 8 == 0 && ldv % 8 == 0 && ldo % 4 == 0 && ldq >= heads_q * FA_HD &&
-                  ldk >= heads_kv * FA_HD && ldv >= heads_kv * FA_HD && ldo >= heads_q * FA_HD,
-                  "causal_attention: bad strides");
-    EGG_CHECK_ARG(q && k && v && o && lens, "causal_attention: NULL pointer");
-    EGG_CHECK_ARG(((uintptr_t)q & 15) == 0 && ((uintptr_t)k & 15) == 0 && ((uintptr_t)v & 15) == 0 && ((uintptr_t)o & 7) == 0 &&
-                  ((uintptr_t)lens & 3) == 0, "causal_attention: q/k/v must be 16-byte aligned, o 8-byte aligned");
-    const int64_t nqb = (N + CA_QB - 1) / CA_QB;
-    EGG_CHECK_ARG(B * heads_q * nqb < (1ll << 31), "causal_attention: grid too large");
-    hipLaunchKernelGGL(k_causal_attn, dim3((unsigned)(B * heads_q * nqb)), dim3(256), 0, as_stream(stream),
-                       (const unsigned short*)q, ldq, (const unsigned short*)k, ldk, (const unsigned short*)v, ldv, lens,
-                       (int)heads_q, (int)(heads_q / heads_kv), (int)N, (int)nqb, scale * 1.4426950408889634f,
-                       (unsigned short*)o, ldo);
-    EGG_CHECK_LAUNCH("causal_attention");
     return EGGROLL_OK;
 }
 

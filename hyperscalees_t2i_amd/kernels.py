@@ -1141,6 +1141,41 @@ def flash_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: fl
 RELBIAS_MAX_N = 512   # RB_NMAX in eggroll_model.hip
 
 
+def _seq_attention(name: str, head_dim: int, q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, lens: torch.Tensor,
+                   B: int, N: int, heads_q: int, heads_kv: int, out: Optional[torch.Tensor], call_args, nbytes: float,
+                   flops: float, desc: str) -> torch.Tensor:
+    """What relbias_ / softcap_ / causal_attention share (k_seq_attn's instances; `name` is the public function's):
+    q [>= B*N, >= heads_q*head_dim], k / v [>= B*N, >= heads_kv*head_dim] 2-D bf16 device views with unit inner
+    stride; lens [B] integer, a CPU tensor range-checked here and copied, a device tensor clamped to [0, N] in the
+    kernel; out None or a bf16 [>= B*N, >= heads_q*head_dim] device view.  call_args = (head, tail): eggroll_<name>'s
+    arguments between v's row stride and lens, and between B and o."""
+    if B < 0 or N < 1 or heads_kv < 1 or heads_q < heads_kv or heads_q % heads_kv:
+        raise ValueError(f"{name}: need B >= 0, N >= 1, heads_q a multiple of heads_kv >= 1 (B={B}, N={N}, "
+                         f"heads_q={heads_q}, heads_kv={heads_kv})")
+    for t, nm, hh in ((q, "q", heads_q), (k, "k", heads_kv), (v, "v", heads_kv)):
+        if (not isinstance(t, torch.Tensor) or t.device.type != "cuda" or t.dtype != torch.bfloat16 or t.dim() != 2
+                or t.stride(1) != 1):
+            raise _lib.EggrollError(f"{name}({nm}): expected a 2-D bf16 device view with unit inner stride")
+        if t.shape[0] < B * N or t.shape[1] < hh * head_dim:
+            raise ValueError(f"{name}: {nm} {tuple(t.shape)} has fewer than B*N={B * N} rows of "
+                             f"heads*{head_dim}={hh * head_dim}")
+    if not isinstance(lens, torch.Tensor) or lens.is_floating_point() or lens.numel() != B:
+        raise ValueError(f"{name}: lens must be an integer tensor of B={B} entries")
+    if lens.device.type == "cpu" and B and (int(lens.min()) < 0 or int(lens.max()) > N):
+        raise ValueError(f"{name}: lens outside [0, {N}]")
+    ln = lens.to(device=q.device, dtype=torch.int32).contiguous()
+    if out is None:
+        out = torch.empty((B * N, heads_q * head_dim), dtype=torch.bfloat16, device=q.device)
+    elif (out.device != q.device or out.dtype != torch.bfloat16 or out.dim() != 2 or out.stride(1) != 1
+          or out.shape[0] < B * N or out.shape[1] < heads_q * head_dim):
+        raise ValueError(f"{name}: out must be a bf16 [>= B*N, >= heads_q*{head_dim}] device view")
+    e0 = OpTimer.begin()
+    _lib.call("eggroll_" + name, q.data_ptr(), q.stride(0), k.data_ptr(), k.stride(0), v.data_ptr(), v.stride(0),
+              *call_args[0], ln.data_ptr(), B, *call_args[1], out.data_ptr(), out.stride(0), _stream(q.device))
+    OpTimer.end(e0, name, nbytes, desc, flops=flops)
+    return out
+
+
 def relbias_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, rel_bias: torch.Tensor, lens: torch.Tensor,
                       B: int, N: int, heads: int, scale: float = 1.0,
                       out: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -1150,38 +1185,17 @@ def relbias_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, rel_bia
     [heads, 2R-1] fp32, R >= N, indexed by key - query; lens [B] integer (a CPU tensor is range-checked here
     and copied; a device tensor is clamped to [0, N] in the kernel).  Rows i >= lens[b] come out zero.
     Returns [B*N, heads*64] bf16 (or writes `out`)."""
-    for t, nm in ((q, "q"), (k, "k"), (v, "v")):
-        if (not isinstance(t, torch.Tensor) or t.device.type != "cuda" or t.dtype != torch.bfloat16 or t.dim() != 2
-                or t.stride(1) != 1):
-            raise _lib.EggrollError(f"relbias_attention({nm}): expected a 2-D bf16 device view with unit inner stride")
-        if t.shape[0] < B * N or t.shape[1] < heads * 64:
-            raise ValueError(f"relbias_attention: {nm} {tuple(t.shape)} has fewer than B*N={B * N} rows of "
-                             f"heads*64={heads * 64}")
-    if not 1 <= N <= RELBIAS_MAX_N or heads < 1 or B < 0:
-        raise ValueError(f"relbias_attention: need 1 <= N <= {RELBIAS_MAX_N}, heads >= 1, B >= 0 (N={N}, heads={heads}, "
-                         f"B={B})")
+    if not 1 <= N <= RELBIAS_MAX_N:
+        raise ValueError(f"relbias_attention: need 1 <= N <= {RELBIAS_MAX_N} (N={N})")
     _dev(rel_bias, "relbias_attention(rel_bias)", torch.float32)
     if rel_bias.dim() != 2 or rel_bias.shape[0] != heads or rel_bias.shape[1] % 2 != 1 or rel_bias.shape[1] < 2 * N - 1:
         raise ValueError(f"relbias_attention: rel_bias {tuple(rel_bias.shape)} must be [heads={heads}, 2R-1] with "
                          f"R >= N={N}")
     R = (rel_bias.shape[1] + 1) // 2
-    if not isinstance(lens, torch.Tensor) or lens.is_floating_point() or lens.numel() != B:
-        raise ValueError(f"relbias_attention: lens must be an integer tensor of B={B} entries")
-    if lens.device.type == "cpu" and B and (int(lens.min()) < 0 or int(lens.max()) > N):
-        raise ValueError(f"relbias_attention: lens outside [0, {N}]")
-    ln = lens.to(device=q.device, dtype=torch.int32).contiguous()
-    if out is None:
-        out = torch.empty((B * N, heads * 64), dtype=torch.bfloat16, device=q.device)
-    elif (out.device != q.device or out.dtype != torch.bfloat16 or out.dim() != 2 or out.stride(1) != 1
-          or out.shape[0] < B * N or out.shape[1] < heads * 64):
-        raise ValueError("relbias_attention: out must be a bf16 [>= B*N, >= heads*64] device view")
-    e0 = OpTimer.begin()
-    _lib.call("eggroll_relbias_attention", q.data_ptr(), q.stride(0), k.data_ptr(), k.stride(0), v.data_ptr(),
-              v.stride(0), rel_bias.data_ptr(), R, ln.data_ptr(), B, heads, N, 64, float(scale), out.data_ptr(),
-              out.stride(0), _stream(q.device))
-    OpTimer.end(e0, "relbias_attention", 2.0 * 4 * B * N * heads * 64 + 4.0 * rel_bias.numel(), f"B{B} N{N} h{heads}",
-                flops=4.0 * B * heads * N * N * 64)
-    return out
+    return _seq_attention(
+        "relbias_attention", 64, q, k, v, lens, B, N, heads, heads, out,
+        ((rel_bias.data_ptr(), R), (heads, N, 64, float(scale))),
+        2.0 * 4 * B * N * heads * 64 + 4.0 * rel_bias.numel(), 4.0 * B * heads * N * N * 64, f"B{B} N{N} h{heads}")
 
 
 def softcap_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, lens: torch.Tensor, B: int, N: int,
@@ -1196,33 +1210,10 @@ def softcap_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, lens: t
     `out`)."""
     if head_dim != 256:
         raise ValueError(f"softcap_attention: head_dim {head_dim} unsupported (256)")
-    if B < 0 or N < 1 or heads_kv < 1 or heads_q < heads_kv or heads_q % heads_kv:
-        raise ValueError(f"softcap_attention: need B >= 0, N >= 1, heads_q a multiple of heads_kv >= 1 (B={B}, N={N}, "
-                         f"heads_q={heads_q}, heads_kv={heads_kv})")
-    for t, nm, hh in ((q, "q", heads_q), (k, "k", heads_kv), (v, "v", heads_kv)):
-        if (not isinstance(t, torch.Tensor) or t.device.type != "cuda" or t.dtype != torch.bfloat16 or t.dim() != 2
-                or t.stride(1) != 1):
-            raise _lib.EggrollError(f"softcap_attention({nm}): expected a 2-D bf16 device view with unit inner stride")
-        if t.shape[0] < B * N or t.shape[1] < hh * 256:
-            raise ValueError(f"softcap_attention: {nm} {tuple(t.shape)} has fewer than B*N={B * N} rows of "
-                             f"heads*256={hh * 256}")
-    if not isinstance(lens, torch.Tensor) or lens.is_floating_point() or lens.numel() != B:
-        raise ValueError(f"softcap_attention: lens must be an integer tensor of B={B} entries")
-    if lens.device.type == "cpu" and B and (int(lens.min()) < 0 or int(lens.max()) > N):
-        raise ValueError(f"softcap_attention: lens outside [0, {N}]")
-    ln = lens.to(device=q.device, dtype=torch.int32).contiguous()
-    if out is None:
-        out = torch.empty((B * N, heads_q * 256), dtype=torch.bfloat16, device=q.device)
-    elif (out.device != q.device or out.dtype != torch.bfloat16 or out.dim() != 2 or out.stride(1) != 1
-          or out.shape[0] < B * N or out.shape[1] < heads_q * 256):
-        raise ValueError("softcap_attention: out must be a bf16 [>= B*N, >= heads_q*256] device view")
-    e0 = OpTimer.begin()
-    _lib.call("eggroll_softcap_attention", q.data_ptr(), q.stride(0), k.data_ptr(), k.stride(0), v.data_ptr(),
-              v.stride(0), ln.data_ptr(), B, heads_q, heads_kv, N, 256, float(scale), float(cap), out.data_ptr(),
-              out.stride(0), _stream(q.device))
-    OpTimer.end(e0, "softcap_attention", 2.0 * 2 * B * N * (heads_q + heads_kv) * 256, f"B{B} N{N} h{heads_q}/{heads_kv}",
-                flops=2.0 * B * heads_q * N * N * 256)
-    return out
+    return _seq_attention(
+        "softcap_attention", 256, q, k, v, lens, B, N, heads_q, heads_kv, out,
+        ((), (heads_q, heads_kv, N, 256, float(scale), float(cap))),
+        2.0 * 2 * B * N * (heads_q + heads_kv) * 256, 2.0 * B * heads_q * N * N * 256, f"B{B} N{N} h{heads_q}/{heads_kv}")
 
 
 def rope_half_(x: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, B: int, N: int, heads: int) -> torch.Tensor:
@@ -1254,33 +1245,10 @@ def causal_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, lens: to
     out zero.  Returns [B*N, heads_q*128] bf16 (or writes `out`)."""
     if head_dim != 128:
         raise ValueError(f"causal_attention: head_dim {head_dim} unsupported (128)")
-    if B < 0 or N < 1 or heads_kv < 1 or heads_q < heads_kv or heads_q % heads_kv:
-        raise ValueError(f"causal_attention: need B >= 0, N >= 1, heads_q a multiple of heads_kv >= 1 (B={B}, N={N}, "
-                         f"heads_q={heads_q}, heads_kv={heads_kv})")
-    for t, nm, hh in ((q, "q", heads_q), (k, "k", heads_kv), (v, "v", heads_kv)):
-        if (not isinstance(t, torch.Tensor) or t.device.type != "cuda" or t.dtype != torch.bfloat16 or t.dim() != 2
-                or t.stride(1) != 1):
-            raise _lib.EggrollError(f"causal_attention({nm}): expected a 2-D bf16 device view with unit inner stride")
-        if t.shape[0] < B * N or t.shape[1] < hh * 128:
-            raise ValueError(f"causal_attention: {nm} {tuple(t.shape)} has fewer than B*N={B * N} rows of "
-                             f"heads*128={hh * 128}")
-    if not isinstance(lens, torch.Tensor) or lens.is_floating_point() or lens.numel() != B:
-        raise ValueError(f"causal_attention: lens must be an integer tensor of B={B} entries")
-    if lens.device.type == "cpu" and B and (int(lens.min()) < 0 or int(lens.max()) > N):
-        raise ValueError(f"causal_attention: lens outside [0, {N}]")
-    ln = lens.to(device=q.device, dtype=torch.int32).contiguous()
-    if out is None:
-        out = torch.empty((B * N, heads_q * 128), dtype=torch.bfloat16, device=q.device)
-    elif (out.device != q.device or out.dtype != torch.bfloat16 or out.dim() != 2 or out.stride(1) != 1
-          or out.shape[0] < B * N or out.shape[1] < heads_q * 128):
-        raise ValueError("causal_attention: out must be a bf16 [>= B*N, >= heads_q*128] device view")
-    e0 = OpTimer.begin()
-    _lib.call("eggroll_causal_attention", q.data_ptr(), q.stride(0), k.data_ptr(), k.stride(0), v.data_ptr(),
-              v.stride(0), ln.data_ptr(), B, heads_q, heads_kv, N, 128, float(scale), out.data_ptr(), out.stride(0),
-              _stream(q.device))
-    OpTimer.end(e0, "causal_attention", 2.0 * 2 * B * N * (heads_q + heads_kv) * 128, f"B{B} N{N} h{heads_q}/{heads_kv}",
-                flops=2.0 * B * heads_q * N * N * 128)
-    return out
+    return _seq_attention(
+        "causal_attention", 128, q, k, v, lens, B, N, heads_q, heads_kv, out,
+        ((), (heads_q, heads_kv, N, 128, float(scale))),
+        2.0 * 2 * B * N * (heads_q + heads_kv) * 128, 2.0 * B * heads_q * N * N * 128, f"B{B} N{N} h{heads_q}/{heads_kv}")
 
 
 def qk_norm_rope_half_(x: torch.Tensor, wq: torch.Tensor, wk: torch.Tensor, eps: float, cos: torch.Tensor,

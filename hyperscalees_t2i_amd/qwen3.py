@@ -21,13 +21,16 @@ UNPINNED (diffusers is not importable here); the oracle of the tests is transfor
 from __future__ import annotations
 
 from dataclasses import dataclass
-from typing import Optional, Tuple
+from functools import partial
+from typing import Tuple
 
 import torch
 import torch.nn.functional as F
 from torch import nn
 
 from . import kernels as K
+from . import text_encoder as TE
+from .text_encoder import _nw, _w, linear as _linear
 
 HEAD_DIM = 128   # eggroll_causal_attention / eggroll_qk_norm_rope_half
 
@@ -61,44 +64,8 @@ class Qwen3Arch:
 
 
 def rope_tables(N: int, head_dim: int = HEAD_DIM, theta: float = 1e6) -> Tuple[torch.Tensor, torch.Tensor]:
-    """Qwen3RotaryEmbedding restated for positions 0..N-1 (default rope type, attention scaling 1): fp32 CPU
-    cos, sin [N, head_dim / 2] — transformers' [N, head_dim] table is this one twice, side by side."""
-    inv_freq = 1.0 / (theta ** (torch.arange(0, head_dim, 2, dtype=torch.int64).float() / head_dim))
-    freqs = torch.arange(N, dtype=torch.int64).float()[:, None] * inv_freq[None, :]
-    return freqs.cos().contiguous(), freqs.sin().contiguous()
-
-
-def _w(*shape) -> nn.Parameter:
-    return nn.Parameter(torch.zeros(*shape, dtype=torch.bfloat16), requires_grad=False)
-
-
-def _nw(C: int) -> nn.Parameter:
-    return nn.Parameter(torch.zeros(1, C, dtype=torch.float32), requires_grad=False)
-
-
-def _gemm_ok(W: torch.Tensor) -> bool:
-    """The r = 0 MFMA GEMM's shape rule (eggroll_lora_gemm: K % 64 == 0; 16-byte output rows)."""
-    return W.shape[1] % 64 == 0 and W.shape[0] % 8 == 0
-
-
-def _linear(x: torch.Tensor, W: torch.Tensor, epi: Optional[str] = None, res: Optional[torch.Tensor] = None):
-    """x [M, K] bf16 @ W^T with the op that follows it: None, "silu", "mul" (res *= y, bf16), "res32" (res += y,
-    the fp32 stream).  On the library's GEMM where its shape rule admits W, else F.linear and the same op."""
-    M = x.shape[0]
-    if _gemm_ok(W):
-        if epi is None:
-            return K.lora_linear_pop(x, W, None, None, 0, 0, 0, 0.0, M)
-        return K.lora_linear_pop_epi(x, W, None, None, 0, 0, 0, 0.0, M, epi, res=res)
-    y = F.linear(x, W)
-    if epi is None:
-        return y
-    if epi == "silu":
-        return F.silu(y)
-    if epi == "mul":
-        return res.mul_(y)
-    if epi == "res32":
-        return res.add_(y.float())
-    raise ValueError(f"qwen3._linear: epi {epi!r} unsupported")
+    """Qwen3RotaryEmbedding restated: text_encoder.rope_tables at this model's defaults."""
+    return TE.rope_tables(N, head_dim, theta)
 
 
 def _norm(x: torch.Tensor, mscale: torch.Tensor, eps: float) -> torch.Tensor:
@@ -145,12 +112,7 @@ class Qwen3Encoder(nn.Module):
         """Random weights, fan-in scaled so activations stay O(1) (timing runs; no checkpoint needed).  Drawn on
         the device the parameters live on."""
         a = self.arch
-        g = torch.Generator(device=self.embed.device).manual_seed(seed)
-
-        def fill(p, std):
-            for r in range(0, p.shape[0], 65536):   # in row chunks: no fp32 copy of a whole matrix
-                q = p[r:r + 65536]
-                q.copy_((torch.randn(q.shape, generator=g, device=p.device) * std).to(p.dtype))
+        fill = partial(TE.fill, generator=torch.Generator(device=self.embed.device).manual_seed(seed))
         fill(self.embed, 0.02)
         for b in self.blocks:
             b.ln_in.zero_()
@@ -171,18 +133,9 @@ class Qwen3Encoder(nn.Module):
         rest padding (finite, not meaningful)."""
         a = self.arch
         dev = self.embed.device
-        B, S = input_ids.shape
-        lens = lens.to(torch.int64).reshape(-1)
-        if lens.numel() != B:
-            raise ValueError(f"Qwen3Encoder: lens has {lens.numel()} entries for {B} prompts")
-        lo, hi = (int(lens.min()), int(lens.max())) if B else (0, 0)
-        if lo < 0 or hi > S:
-            raise ValueError(f"Qwen3Encoder: lens outside [0, {S}]")
-        N = max(hi, 1)
+        B, N, ids, ln = TE.trim_batch("Qwen3Encoder", input_ids, lens, dev)
         if B == 0:
             return torch.empty((0, N, a.hidden_size), dtype=torch.bfloat16, device=dev)
-        ids = input_ids[:, :N].to(dev).reshape(-1)
-        ln = lens.to(device=dev, dtype=torch.int32)
         cos, sin = (t.to(dev) for t in rope_tables(N, a.head_dim, a.rope_theta))
         x = F.embedding(ids, self.embed).float()   # the fp32 residual stream [B*N, hidden]
         qw, kw = a.q_width, a.kv_width

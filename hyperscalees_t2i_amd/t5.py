@@ -19,13 +19,15 @@ from __future__ import annotations
 
 import math
 from dataclasses import dataclass
-from typing import Optional
+from functools import partial
 
 import torch
 import torch.nn.functional as F
 from torch import nn
 
 from . import kernels as K
+from . import text_encoder as TE
+from .text_encoder import _w, linear as _linear
 
 MAX_TOKENS = K.RELBIAS_MAX_N   # the reference's max_length (models/Infinity.py:304)
 
@@ -74,36 +76,6 @@ def rel_bias_table(weight: torch.Tensor, R: int, num_buckets: int = 32, max_dist
     return weight.detach().float()[bucket.to(weight.device)].t().contiguous()
 
 
-def _w(*shape) -> nn.Parameter:
-    return nn.Parameter(torch.zeros(*shape, dtype=torch.bfloat16), requires_grad=False)
-
-
-def _gemm_ok(W: torch.Tensor) -> bool:
-    """The r = 0 MFMA GEMM's shape rule (eggroll_lora_gemm: K % 64 == 0; 16-byte output rows)."""
-    return W.shape[1] % 64 == 0 and W.shape[0] % 8 == 0
-
-
-def _linear(x: torch.Tensor, W: torch.Tensor, epi: Optional[str] = None, res: Optional[torch.Tensor] = None):
-    """x [M, K] bf16 @ W^T with the op that follows it: None, "gelu" (tanh), "mul" (res *= y, bf16),
-    "res32" (res += y, the fp32 stream).  On the library's GEMM where its shape rule admits W, else F.linear
-    and the same op."""
-    M = x.shape[0]
-    if _gemm_ok(W):
-        if epi is None:
-            return K.lora_linear_pop(x, W, None, None, 0, 0, 0, 0.0, M)
-        return K.lora_linear_pop_epi(x, W, None, None, 0, 0, 0, 0.0, M, epi, res=res)
-    y = F.linear(x, W)
-    if epi is None:
-        return y
-    if epi == "gelu":
-        return F.gelu(y, approximate="tanh")
-    if epi == "mul":
-        return res.mul_(y)
-    if epi == "res32":
-        return res.add_(y)
-    raise ValueError(f"t5._linear: epi {epi!r} unsupported")
-
-
 class T5Block(nn.Module):
     def __init__(self, a: T5Arch):
         super().__init__()
@@ -131,10 +103,7 @@ class T5Encoder(nn.Module):
     def init_weights(self, seed: int = 0):
         """Random weights at T5's initialisation scales (timing runs; no checkpoint needed)."""
         a = self.arch
-        g = torch.Generator().manual_seed(seed)
-
-        def fill(p, std):
-            p.copy_((torch.randn(p.shape, generator=g) * std).to(p.dtype))
+        fill = partial(TE.fill, generator=torch.Generator().manual_seed(seed))   # drawn on the CPU
         fill(self.embed, 1.0)
         fill(self.rel_bias, a.d_model ** -0.5)
         for b in self.blocks:
@@ -156,20 +125,11 @@ class T5Encoder(nn.Module):
         rest padding (finite, not meaningful)."""
         a = self.arch
         dev = self.embed.device
-        B, S = input_ids.shape
-        lens = lens.to(torch.int64).reshape(-1)
-        if lens.numel() != B:
-            raise ValueError(f"T5Encoder: lens has {lens.numel()} entries for {B} prompts")
-        lo, hi = (int(lens.min()), int(lens.max())) if B else (0, 0)
-        if lo < 0 or hi > S:
-            raise ValueError(f"T5Encoder: lens outside [0, {S}]")
-        N = max(hi, 1)
+        B, N, ids, ln = TE.trim_batch("T5Encoder", input_ids, lens, dev)
         if N > MAX_TOKENS:
             raise ValueError(f"T5Encoder: {N} tokens in a prompt (at most {MAX_TOKENS})")
         if B == 0:
             return torch.empty((0, N, a.d_model), dtype=torch.bfloat16, device=dev)
-        ids = input_ids[:, :N].to(dev).reshape(-1)
-        ln = lens.to(device=dev, dtype=torch.int32)
         table = rel_bias_table(self.rel_bias, N, a.num_buckets, a.max_distance)
         x = F.embedding(ids, self.embed).float()               # the fp32 residual stream [B*N, d_model]
         inner = a.inner
