@@ -52,6 +52,8 @@ SIGNATURES = {
                                      vp, vp]),
     "eggroll_subpixel_shortcut_f32": (C.c_int, [vp, vp, vp, vp, vp, i64, i64, i64, i64, i64, vp]),
     "eggroll_gated_residual_f32": (C.c_int, [vp, vp, vp, i32, i64, i64, i64, i64, vp, vp]),
+    "eggroll_scm_step": (C.c_int, [vp, i64, vp, i32, vp, i64, i64, f32, f32, f32, f32, f32, f32, f32, f32, f32, i32, vp,
+                                   vp, vp, vp]),
     "eggroll_resid_layernorm": (C.c_int, [vp, i64, vp, i64, i64, i64, f32, vp, vp, vp, vp]),
     "eggroll_dwconv_pw_nhwc": (C.c_int, [vp, vp, vp, i64, i64, i64, i64, i32, vp, vp]),
     "eggroll_dwconv_nhwc_sel": (C.c_int, [vp, vp, vp, i64, i64, i64, i64, i32, i32, i32, vp, i32, vp]),

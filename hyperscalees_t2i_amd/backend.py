@@ -18,7 +18,7 @@ import torch
 
 from .es import get_trainable_params_and_shapes, repeat_batches, sample_classes_unique, sample_indices_unique
 from .lora import lora_modules
-from .pipeline import SanaOneStep
+from .pipeline import SanaOneStep, SanaPipelineES
 from .sana import SANA_LORA_TARGETS, SANA_SPRINT_1_6B, SanaArch, attach_lora
 from .var import VAR_LORA_TARGETS, VARArch, VARClassGenerator
 
@@ -105,6 +105,9 @@ class SanaConfig:
     # auto_encode_if_missing: one local directory with the Gemma-2 checkpoint and its tokenizer files; empty:
     # model_name/text_encoder + model_name/tokenizer (the diffusers layout)
     text_encoder_path: str = ""
+    # backend_mode "pipeline": transformer forwards per image (SanaPipelineES; the scheduler's default
+    # intermediate timestep allows exactly 2)
+    num_inference_steps: int = 2
 
 
 def synthetic_prompt_data(P: int = 4, seq: int = 300, dim: int = 2304, seed: int = 0) -> Dict[str, Any]:
@@ -120,12 +123,12 @@ def synthetic_prompt_data(P: int = 4, seq: int = 300, dim: int = 2304, seed: int
 
 class SanaBackend(ESBackend):
     def __init__(self, device: str, cfg: SanaConfig):
-        if cfg.backend_mode != "one_step":
-            raise ValueError(f"Unknown/unsupported Sana backend_mode: {cfg.backend_mode} (one_step only)")
+        if cfg.backend_mode not in ("one_step", "pipeline"):
+            raise ValueError(f"Unknown/unsupported Sana backend_mode: {cfg.backend_mode} (one_step or pipeline)")
         self.name = f"sana_{cfg.backend_mode}"
         self.device = device
         self.cfg = cfg
-        self.es_model: Optional[SanaOneStep] = None
+        self.es_model: Optional[Union[SanaOneStep, SanaPipelineES]] = None
         self.prompt_data = None
         self.base_prompt_embeds = None
         self.base_attention_mask = None
@@ -134,6 +137,14 @@ class SanaBackend(ESBackend):
 
     def _dtype(self) -> torch.dtype:
         return torch.bfloat16 if self.cfg.dtype_latents.lower() == "bfloat16" else torch.float16
+
+    def _build_model(self, **kw):
+        """The generator class of backend_mode (es_backend.py:128-190): SanaOneStep or SanaPipelineES."""
+        c = self.cfg
+        if c.backend_mode == "pipeline":
+            return SanaPipelineES(c.model_name, device=self.device, DTYPE=self._dtype(), sigma_data=0.5,
+                                  num_inference_steps=c.num_inference_steps, **kw)
+        return SanaOneStep(c.model_name, device=self.device, DTYPE=self._dtype(), sigma_data=0.5, **kw)
 
     def _load_or_encode_prompts(self):
         """es_backend.py:112-170: an encoded file; with auto_encode_if_missing, that file encoded from
@@ -149,8 +160,7 @@ class SanaBackend(ESBackend):
                 txt = Path(c.prompts_txt_path)
                 if not txt.is_file():
                     raise FileNotFoundError(f"prompts_txt_path not found: {txt}")
-                tmp = SanaOneStep(c.model_name, device=self.device, DTYPE=self._dtype(), sigma_data=0.5,
-                                  text_encoder_path=c.text_encoder_path or None, encode_only=True)
+                tmp = self._build_model(text_encoder_path=c.text_encoder_path or None, encode_only=True)
                 tmp.encode_prompts(txt, enc, batch_size=int(c.encode_batch_size), overwrite=True)
                 tmp.drop_text_encoder()
                 del tmp
@@ -169,9 +179,9 @@ class SanaBackend(ESBackend):
     def init_and_attach_lora(self):
         self._load_or_encode_prompts()
         c = self.cfg
-        self.es_model = SanaOneStep(c.model_name, device=self.device, DTYPE=self._dtype(), sigma_data=0.5, arch=c.arch,
-                                    vae_widths=c.vae_widths, vae_layers=c.vae_layers, weight_seed=c.weight_seed,
-                                    vae_chunk=c.vae_chunk, synthetic_weights=c.synthetic_weights)
+        self.es_model = self._build_model(arch=c.arch, vae_widths=c.vae_widths, vae_layers=c.vae_layers,
+                                          weight_seed=c.weight_seed, vae_chunk=c.vae_chunk,
+                                          synthetic_weights=c.synthetic_weights)
         n = attach_lora(self.es_model.transformer, c.lora_r, c.lora_alpha, c.lora_target_modules)
         if n == 0:
             raise RuntimeError("no LoRA target module matched")
@@ -221,9 +231,15 @@ class SanaBackend(ESBackend):
         instead of all images sharing one batched draw from `seed`."""
         pe, am = self._gather(flat_ids)
         latents = None
+        if flat_seeds is not None and len(flat_seeds) != len(flat_ids):
+            raise ValueError(f"flat_seeds has {len(flat_seeds)} entries, flat_ids {len(flat_ids)}")
+        if self.cfg.backend_mode == "pipeline":   # each image's generator draws its latents, then its step noises
+            images, _ = self.es_model.generate_one_batch(
+                prompt_embeds=pe, prompt_attention_mask=am, seed=seed, guidance_scale=guidance_scale,
+                width_latent=self.cfg.width_latent, height_latent=self.cfg.height_latent,
+                image_seeds=None if flat_seeds is None else [int(s) for s in flat_seeds])
+            return images
         if flat_seeds is not None:
-            if len(flat_seeds) != len(flat_ids):
-                raise ValueError(f"flat_seeds has {len(flat_seeds)} entries, flat_ids {len(flat_ids)}")
             m = self.es_model
             latents = torch.cat([m._latents(1, int(s), self.cfg.height_latent, self.cfg.width_latent)
                                  for s in flat_seeds])

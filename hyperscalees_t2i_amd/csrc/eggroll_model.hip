@@ -622,6 +622,77 @@ __global__ __launch_bounds__(256) void k_gated_residual_f32(float* __restrict__ 
     }
 }
 
+// One SCM / trigflow sampler step between two transformer forwards (or before the decoder), see
+// eggroll_scm_step in include/eggroll.h.  Member = blockIdx.y; thread i of a member handles the
+// 4-element chunk i (128-bit loads and stores; nvec chunks, 0 when a pointer or the member length
+// rules them out) or, past the chunks, one element of the scalar tail.  RD: 0 none, 1 fp16, 2 bf16.
+// x_next may alias x: every element is read and written by the same thread.
+struct ScmScalars {
+    float in_scale, coef_m, coef_eps, cos_t, sin_t, cos_n, sin_n_sd, in_scale_next, out_scale;
+};
+
+template <int RD>
+__device__ __forceinline__ float scm_rnd(float v) {
+    if (RD == 1) return (float)(_Float16)v;
+    if (RD == 2) return b2f(f2b(v));
+    return v;
+}
+
+template <int RD>
+__device__ __forceinline__ void scm_elem(const ScmScalars& s, float x, float e, float nz, float& x_next, float& m_next,
+                                         float& x0_out) {
+    const float m = scm_rnd<RD>(x * s.in_scale);
+    const float pred = __builtin_fmaf(s.coef_m, m, s.coef_eps * scm_rnd<RD>(e));
+    const float x0 = __builtin_fmaf(s.cos_t, x, -(s.sin_t * pred));
+    x_next = __builtin_fmaf(s.cos_n, x0, s.sin_n_sd * nz);
+    m_next = scm_rnd<RD>(x_next * s.in_scale_next);
+    x0_out = x0 * s.out_scale;
+}
+
+template <int RD, int E32>
+__global__ __launch_bounds__(256) void k_scm_step(const float* x, int64_t x_member_stride, const void* __restrict__ eps,
+                                                  const float* __restrict__ noise, int64_t n, int64_t nvec,
+                                                  ScmScalars s, float* x_next, float* __restrict__ m_next,
+                                                  float* __restrict__ x0_out) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t k = blockIdx.y;
+    const float* xm = x + k * x_member_stride;
+    const int64_t mo = k * n;  // this member's offset into eps and the outputs
+    if (i < nvec) {
+        const int64_t o = i * 4;
+        const float4 xv = *reinterpret_cast<const float4*>(xm + o);
+        float ev[4], nv[4] = {0.f, 0.f, 0.f, 0.f};
+        if (E32) {
+            const float4 q = *reinterpret_cast<const float4*>((const float*)eps + mo + o);
+            ev[0] = q.x, ev[1] = q.y, ev[2] = q.z, ev[3] = q.w;
+        } else {
+            const u16x4m q = *reinterpret_cast<const u16x4m*>((const unsigned short*)eps + mo + o);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) ev[j] = b2f(q[j]);
+        }
+        if (noise) {
+            const float4 q = *reinterpret_cast<const float4*>(noise + o);
+            nv[0] = q.x, nv[1] = q.y, nv[2] = q.z, nv[3] = q.w;
+        }
+        const float xs[4] = {xv.x, xv.y, xv.z, xv.w};
+        float xn[4], mn[4], xo[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) scm_elem<RD>(s, xs[j], ev[j], nv[j], xn[j], mn[j], xo[j]);
+        if (x_next) *reinterpret_cast<float4*>(x_next + mo + o) = float4{xn[0], xn[1], xn[2], xn[3]};
+        if (m_next) *reinterpret_cast<float4*>(m_next + mo + o) = float4{mn[0], mn[1], mn[2], mn[3]};
+        if (x0_out) *reinterpret_cast<float4*>(x0_out + mo + o) = float4{xo[0], xo[1], xo[2], xo[3]};
+        return;
+    }
+    const int64_t o = nvec * 4 + (i - nvec);
+    if (o >= n) return;
+    const float e = E32 ? ((const float*)eps)[mo + o] : b2f(((const unsigned short*)eps)[mo + o]);
+    float xn, mn, xo;
+    scm_elem<RD>(s, xm[o], e, noise ? noise[o] : 0.f, xn, mn, xo);
+    if (x_next) x_next[mo + o] = xn;
+    if (m_next) m_next[mo + o] = mn;
+    if (x0_out) x0_out[mo + o] = xo;
+}
+
 // y = act(bf16(y + bias[c])) in place (conv bias folded into the activation pass; torch's conv2d
 // with bias on MIOpen runs the bias as its own add_ pass).  act: 0 none, 1 relu, 2 silu.
 __global__ __launch_bounds__(256) void k_bias_act(unsigned short* __restrict__ y, const unsigned short* __restrict__ bias,
@@ -2093,6 +2164,45 @@ extern "C" int eggroll_gated_residual_f32(float* x, const void* y, const void* g
                        (const unsigned short*)y, gate, gate_f32, gstride, rows_per_group, (int)C, total,
                        (unsigned short*)shadow);
     EGG_CHECK_LAUNCH("gated_residual_f32");
+    return EGGROLL_OK;
+}
+
+extern "C" int eggroll_scm_step(const float* x, int64_t x_member_stride, const void* eps, int32_t eps_f32,
+                                const float* noise, int64_t members, int64_t n, float in_scale, float coef_m,
+                                float coef_eps, float cos_t, float sin_t, float cos_n, float sin_n_sd,
+                                float in_scale_next, float out_scale, int32_t round_dtype, float* x_next,
+                                float* m_next, float* x0_out, void* stream) {
+    EGG_CHECK_ARG(members > 0 && members <= 65535 && n > 0 && x_member_stride >= 0,
+                  "scm_step: bad sizes (members %lld in 1..65535, n %lld > 0, x_member_stride %lld >= 0)",
+                  (long long)members, (long long)n, (long long)x_member_stride);
+    EGG_CHECK_ARG(round_dtype >= 0 && round_dtype <= 2, "scm_step: round_dtype %d is not 0 (none), 1 (fp16) or 2 (bf16)",
+                  (int)round_dtype);
+    EGG_CHECK_ARG(eps_f32 == 0 || eps_f32 == 1, "scm_step: eps_f32 must be 0 or 1");
+    EGG_CHECK_ARG(x && eps, "scm_step: NULL x or eps");
+    EGG_CHECK_ARG(noise || !x_next, "scm_step: x_next needs noise (noise is NULL)");
+    EGG_CHECK_ARG(!(x_next == x && x_member_stride != n),
+                  "scm_step: x_next may alias x only when every member has its own x (x_member_stride == n)");
+    auto al = [](const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) == 0; };
+    const bool vec = al(x, 16) && al(eps, eps_f32 ? 16 : 8) && al(noise, 16) && al(x_next, 16) && al(m_next, 16) &&
+                     al(x0_out, 16) && (members == 1 || (n % 4 == 0 && x_member_stride % 4 == 0));
+    const int64_t nvec = vec ? n / 4 : 0;
+    const int64_t threads = nvec + (n - 4 * nvec);
+    const dim3 grid((unsigned)((threads + 255) / 256), (unsigned)members);
+    const ScmScalars s{in_scale, coef_m, coef_eps, cos_t, sin_t, cos_n, sin_n_sd, in_scale_next, out_scale};
+#define EGG_SCM(RD, E32)                                                                                          \
+    hipLaunchKernelGGL((k_scm_step<RD, E32>), grid, dim3(256), 0, as_stream(stream), x, x_member_stride, eps, noise, n, \
+                       nvec, s, x_next, m_next, x0_out)
+    if (eps_f32) {
+        if (round_dtype == 0) EGG_SCM(0, 1);
+        else if (round_dtype == 1) EGG_SCM(1, 1);
+        else EGG_SCM(2, 1);
+    } else {
+        if (round_dtype == 0) EGG_SCM(0, 0);
+        else if (round_dtype == 1) EGG_SCM(1, 0);
+        else EGG_SCM(2, 0);
+    }
+#undef EGG_SCM
+    EGG_CHECK_LAUNCH("scm_step");
     return EGGROLL_OK;
 }
 

@@ -781,6 +781,42 @@ def gated_residual_f32_(x: torch.Tensor, y: torch.Tensor, gate: Optional[torch.T
     OpTimer.end(e0, "gated_residual_f32", (10.0 + (2 if shadow is not None else 0)) * x.numel(), f"rows{x.numel() // C}")
     return x
 
+def scm_step(x: torch.Tensor, eps: torch.Tensor, noise: Optional[torch.Tensor], scalars: Sequence[float],
+             round_dtype: int, members: int, x_next: Optional[torch.Tensor] = None,
+             m_next: Optional[torch.Tensor] = None, x0_out: Optional[torch.Tensor] = None) -> None:
+    """One SCM / trigflow sampler step (eggroll_scm_step, see include/eggroll.h).  eps: `members` members of
+    n elements each, fp32 or bf16; x fp32: one member's n elements (shared by all) or all members'; noise fp32
+    [n] (None on the last step); scalars: (in_scale, coef_m, coef_eps, cos_t, sin_t, cos_n, sin_n_sd,
+    in_scale_next, out_scale); round_dtype 0 none / 1 fp16 / 2 bf16.  Writes the fp32 outputs that are given
+    (each eps-sized; x_next may be x itself when every member has its own x)."""
+    _dev(x, "scm_step(x)", torch.float32)
+    _dev(eps, "scm_step(eps)")
+    if eps.dtype not in (torch.float32, torch.bfloat16):
+        raise _lib.EggrollError(f"scm_step(eps): expected float32 or bfloat16, got {eps.dtype}")
+    members = int(members)
+    n = eps.numel() // members if members > 0 and eps.numel() % members == 0 else 0
+    sized = n > 0      # else the library reports the bad sizes
+    if sized and x.numel() not in (n, members * n):
+        raise _lib.EggrollError(f"scm_step(x): {x.numel()} elements, expected {n} (shared) or {members * n}")
+    if noise is not None and _dev(noise, "scm_step(noise)", torch.float32).numel() != n and sized:
+        raise _lib.EggrollError(f"scm_step(noise): {noise.numel()} elements, expected {n}")
+    nout = 0
+    for name, t in (("x_next", x_next), ("m_next", m_next), ("x0_out", x0_out)):
+        if t is not None:
+            nout += 1
+            _dev(t, f"scm_step({name})", torch.float32)
+            if sized and t.numel() != members * n and not (t is x and name == "x_next"):   # that alias: the library's error
+                raise _lib.EggrollError(f"scm_step({name}): {t.numel()} elements, expected {members * n}")
+    if len(scalars) != 9:
+        raise _lib.EggrollError(f"scm_step: 9 scalars expected, got {len(scalars)}")
+    e0 = OpTimer.begin()
+    _lib.call("eggroll_scm_step", x.data_ptr(), n if x.numel() == members * n else 0, eps.data_ptr(),
+              int(eps.dtype == torch.float32), _p(noise), members, n, *[float(v) for v in scalars], int(round_dtype),
+              _p(x_next), _p(m_next), _p(x0_out), _stream(x.device))
+    OpTimer.end(e0, "scm_step", float(x.numel() * 4 + eps.numel() * eps.element_size() + 4 * n * (noise is not None)
+                                      + 4 * nout * members * n), f"n{n}x{members}")
+
+
 def resid_layernorm_(h: torch.Tensor, y: Optional[torch.Tensor], w: torch.Tensor, b: torch.Tensor, eps: float,
                      out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """h [..., C] fp32 (rows may be strided: a [n, T, C] stream or its [:, 0] rows) += y (bf16, same row

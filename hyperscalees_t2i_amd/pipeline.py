@@ -11,12 +11,15 @@ One-step SCM / trigflow math exactly as the reference (models/SanaSprint.py:78-1
   x0 = (0.267 latents - 0.964 pred) / sigma_data;  image = vae.decode(x0 / scaling_factor)
 Common random numbers: every member uses the same latents (seed = epoch) and prompts
 (unifed_es.py:163), so latents are drawn once and broadcast over members.
+
+The multi-step sampler (models/SanaSprint.py:280-502 `SanaPipelineES`) follows below SanaOneStep; its math is
+in that class's docstring.
 """
 from __future__ import annotations
 
 import math
 from pathlib import Path
-from typing import Any, List, Optional, Sequence, Tuple
+from typing import Any, List, NamedTuple, Optional, Sequence, Tuple
 
 import torch
 
@@ -43,10 +46,11 @@ class ESBaseModel:
         raise NotImplementedError("Subclasses must implement encode_prompts()")
 
 
-def load_prompts_from_txt(path) -> List[str]:
-    """models/SanaSprint.py:165-169: one prompt per line; blank lines and # lines are skipped."""
+def load_prompts_from_txt(path, keep_comments: bool = False) -> List[str]:
+    """models/SanaSprint.py:165-169: one prompt per line; blank lines and # lines are skipped.
+    keep_comments: the loader of the pipeline class (models/SanaSprint.py:329-332), which skips blank lines only."""
     lines = Path(path).read_text(encoding="utf-8").splitlines()
-    return [ln.strip() for ln in lines if ln.strip() and not ln.strip().startswith("#")]
+    return [ln.strip() for ln in lines if ln.strip() and (keep_comments or not ln.strip().startswith("#"))]
 
 
 class GemmaPromptEncoder:
@@ -118,12 +122,13 @@ class GemmaPromptEncoder:
 
     @torch.no_grad()
     def encode_file(self, prompts_txt_path, encoded_save_path, batch_size: int = 4,
-                    complex_human_instruction=None) -> dict:
+                    complex_human_instruction=None, keep_comments: bool = False) -> dict:
         """models/SanaSprint.py:195-277: the .txt's prompts -> {"prompts", "prompt_embeds" [P, 300, C] fp16 CPU,
         "prompt_attention_mask" [P, 300] int64 CPU}, saved with torch.save and returned."""
-        prompts = load_prompts_from_txt(prompts_txt_path)
+        prompts = load_prompts_from_txt(prompts_txt_path, keep_comments)
         if not prompts:
-            raise ValueError(f"{prompts_txt_path}: no prompts (blank and # lines are skipped)")
+            raise ValueError(f"{prompts_txt_path}: no prompts (blank {'lines' if keep_comments else 'and # lines'} "
+                             f"are skipped)")
         embeds, masks = [], []
         for start in range(0, len(prompts), max(int(batch_size), 1)):
             e, m = self.encode(self.preprocess(prompts[start:start + max(int(batch_size), 1)]),
@@ -162,13 +167,16 @@ def tokenize_for_sana(tokenizer, prompts: Sequence[str], complex_human_instructi
     return tok.input_ids, tok.attention_mask
 
 
-class SanaOneStep(ESBaseModel):
-    """models/SanaSprint.py:10-60.  Weights: `model_name` is a LOCAL diffusers-format directory
+class _SanaStack(ESBaseModel):
+    """What SanaOneStep and SanaPipelineES share: the transformer + DC-AE build and the prompt cache.
+    Weights: `model_name` is a LOCAL diffusers-format directory
     (transformer/ + vae/, loaded by checkpoints.py; the architecture comes from its config.json files,
     `arch` / `vae_*` are ignored), or — only with synthetic_weights=True — anything, in which case
     the given architecture is built with seeded synthetic weights (throughput runs).
     Anything else raises FileNotFoundError: there is no hub access, and silently substituting random
     weights for a named checkpoint would produce plausible-looking but meaningless numbers."""
+
+    KEEP_COMMENT_PROMPTS = False   # the prompt .txt loader keeps # lines (load_prompts_from_txt)
 
     def __init__(self, model_name: str = "Efficient-Large-Model/Sana_Sprint_1.6B_1024px_diffusers",
                  device: str = "cuda:0", DTYPE: torch.dtype = torch.float16, sigma_data: float = 0.5,
@@ -207,7 +215,7 @@ class SanaOneStep(ESBaseModel):
         else:
             why = ("exists but lacks transformer/ or vae/" if root.exists()
                    else "is not a local directory (no hub downloads offline)")
-            raise FileNotFoundError(f"SanaOneStep: model_name {str(model_name)!r} {why}; pass a local diffusers "
+            raise FileNotFoundError(f"{type(self).__name__}: model_name {str(model_name)!r} {why}; pass a local diffusers "
                                     f"model directory, or synthetic_weights=True for seeded random weights")
         self.transformer_config = arch
         self.vae_chunk = vae_chunk
@@ -229,13 +237,18 @@ class SanaOneStep(ESBaseModel):
             cc = self.transformer_config.caption_channels if self.transformer is not None else None
             self._prompt_encoder = GemmaPromptEncoder(self.model_name, self.device, self.text_encoder_path, cc)
             self.tokenizer, self.text_encoder = self._prompt_encoder.tokenizer, self._prompt_encoder.encoder
-        return self._prompt_encoder.encode_file(prompts_txt_path, enc, batch_size, complex_human_instruction)
+        return self._prompt_encoder.encode_file(prompts_txt_path, enc, batch_size, complex_human_instruction,
+                                                self.KEEP_COMMENT_PROMPTS)
 
     def drop_text_encoder(self):
         if self._prompt_encoder is not None:
             self._prompt_encoder.drop()
         self._prompt_encoder = None
         self.text_encoder = None
+
+
+class SanaOneStep(_SanaStack):
+    """models/SanaSprint.py:10-60: the one-step generator (build and prompt cache: _SanaStack)."""
 
     # ---- shared one-step math -------------------------------------------------------
     def _latents(self, b: int, seed: int, h: int, w: int) -> torch.Tensor:
@@ -308,6 +321,232 @@ class SanaOneStep(ESBaseModel):
             latents = self._latents(b, seed, height_latent, width_latent)
             imgs, _ = self._one_step(latents, prompt_embeds, prompt_attention_mask, guidance_scale, reps=n,
                                      prompt_index=prompt_index)
+        finally:
+            set_population(self.transformer, None)
+            self.ctx.theta_pop = None
+        return imgs
+
+
+# ---------------------------------------------------------------------------------------
+# Multi-step SCM sampler (models/SanaSprint.py:280-502 `SanaPipelineES`)
+# ---------------------------------------------------------------------------------------
+
+# True: the arithmetic between two forwards is one eggroll_scm_step launch; False: its torch form
+# (_step_torch, about fifteen elementwise launches) — kept for A/B runs and as what the kernel is tested against
+FUSE_SCM_STEP = True
+
+SCM_MAX_TIMESTEPS = 1.57080
+SCM_INTERMEDIATE_TIMESTEPS = 1.3
+_ROUND_DTYPES = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}
+
+
+def scm_timesteps(num_inference_steps: int, max_timesteps: float = SCM_MAX_TIMESTEPS,
+                  intermediate_timesteps: Optional[float] = SCM_INTERMEDIATE_TIMESTEPS) -> List[float]:
+    """SCMScheduler.set_timesteps: [max, intermediate, 0] (two steps only), or with intermediate_timesteps=None
+    linspace(max, 0, steps + 1).  The sampler loops over all but the last."""
+    steps = int(num_inference_steps)
+    if steps < 1:
+        raise ValueError(f"num_inference_steps must be >= 1, got {num_inference_steps}")
+    if intermediate_timesteps is not None:
+        if steps != 2:
+            raise ValueError("Intermediate timesteps for SCM is not supported when num_inference_steps != 2.")
+        return [float(max_timesteps), float(intermediate_timesteps), 0.0]
+    return torch.linspace(float(max_timesteps), 0.0, steps + 1, dtype=torch.float64).tolist()
+
+
+def scm_s(t: float) -> float:
+    """The SCM timestep the transformer is conditioned on: sin t / (cos t + sin t)."""
+    return math.sin(t) / (math.cos(t) + math.sin(t))
+
+
+class ScmStepScalars(NamedTuple):
+    """The scalars of one sampler step (eggroll_scm_step), fp64 on the host."""
+    in_scale: float
+    coef_m: float
+    coef_eps: float
+    cos_t: float
+    sin_t: float
+    cos_n: float
+    sin_n_sd: float
+    in_scale_next: float
+    out_scale: float
+
+
+def scm_step_scalars(t: float, n: float, sigma_data: float, out_scale: float = 1.0) -> ScmStepScalars:
+    """Angular time t of this step, n of the next.  The pipeline feeds the transformer m = x / sigma_data * q with
+    q = sqrt(s^2 + (1 - s)^2) and combines pred = ((1 - 2s) m + (1 - 2s + 2s^2) eps) / q * sigma_data; the
+    scheduler takes x0 = cos t x - sin t pred and x_next = cos n x0 + sin n sigma_data noise."""
+    s, sn = scm_s(t), scm_s(n)
+    q, qn = math.sqrt(s * s + (1 - s) ** 2), math.sqrt(sn * sn + (1 - sn) ** 2)
+    return ScmStepScalars(q / sigma_data, (1 - 2 * s) * sigma_data / q, (1 - 2 * s + 2 * s * s) * sigma_data / q,
+                          math.cos(t), math.sin(t), math.cos(n), math.sin(n) * sigma_data, qn / sigma_data,
+                          float(out_scale))
+
+
+def _rnd(v: torch.Tensor, round_dtype: int) -> torch.Tensor:
+    """fp32 -> the model dtype and back (round_dtype 0 none, 1 fp16, 2 bf16)."""
+    if round_dtype == 0:
+        return v.float()
+    return v.to(torch.float16 if round_dtype == 1 else torch.bfloat16).float()
+
+
+def _step_torch(x, eps, noise, sc: ScmStepScalars, round_dtype: int, members: int = 1, last: bool = False):
+    """The torch form of eggroll_scm_step on the same fp32 scalars: (x_next, m_next, None), or on the last step
+    (None, None, x0_out), each shaped like eps.  x: one member's elements (shared) or every member's."""
+    c = ScmStepScalars(*[float(torch.tensor(v, dtype=torch.float32)) for v in sc])
+    n = eps.numel() // members
+    xm = x.float().reshape(-1, n)                                  # [1 or members, n]
+    m = _rnd(xm * c.in_scale, round_dtype)
+    pred = c.coef_m * m + c.coef_eps * _rnd(eps.float().reshape(members, n), round_dtype)
+    x0 = c.cos_t * xm - c.sin_t * pred
+    if last:
+        return None, None, (x0 * c.out_scale).reshape(eps.shape)
+    x_next = c.cos_n * x0 + c.sin_n_sd * noise.float().reshape(1, n)
+    return x_next.reshape(eps.shape), _rnd(x_next * c.in_scale_next, round_dtype).reshape(eps.shape), None
+
+
+class SanaPipelineES(_SanaStack):
+    """models/SanaSprint.py:280-502: the multi-step Sana-Sprint sampler (num_inference_steps transformer
+    forwards, two by default), with the population entry point of SanaOneStep.  The reference wraps diffusers'
+    SanaSprintPipeline; the sampler here is restated from the published SanaSprintPipeline.__call__ and
+    SCMScheduler — PARITY WITH DIFFUSERS UNPINNED, diffusers is not importable here:
+      timesteps [1.57080, 1.3, 0] (SCMScheduler.set_timesteps); one Generator(seed) draws the fp32 initial
+      latents (x sigma_data) and then one fp32 noise per step, the last included (its value is unused);
+      per step at angular time t, s = sin t / (cos t + sin t), q = sqrt(s^2 + (1 - s)^2):
+        m = DTYPE(x / sigma_data * q);  eps = transformer(m, DTYPE(s), prompt, mask, guidance)
+        pred = ((1 - 2s) m + (1 - 2s + 2s^2) DTYPE(eps)) / q * sigma_data
+        x0 = cos t x - sin t pred;  x = cos t' x0 + sin t' sigma_data noise   (t' the next time)
+      image = vae.decode(x0 / sigma_data / scaling_factor) after the last step.
+    Everything between two forwards is one eggroll_scm_step launch over all members (FUSE_SCM_STEP); the
+    per-member state stays token-major [members * b, h * w, C] fp32, and the transformer and the decoder get
+    NCHW views of it.  Two departures from the reference: the combine runs in fp32 where diffusers promotes
+    fp16 operands, and width_latent / height_latent are honoured (the reference hard-codes 1024 px = 32 x 32).
+    There is no nan_to_num (the pipeline has none; the engine masks a non-finite member).  Latents and step
+    noise are common random numbers: the reference reseeds the generator for every member."""
+
+    KEEP_COMMENT_PROMPTS = True   # models/SanaSprint.py:329-332
+
+    def __init__(self, model_name: str = "Efficient-Large-Model/Sana_Sprint_1.6B_1024px_diffusers",
+                 device: str = "cuda:0", DTYPE: torch.dtype = torch.float16, sigma_data: float = 0.5,
+                 num_inference_steps: int = 2, arch: SanaArch = SANA_SPRINT_1_6B,
+                 vae_widths=(128, 256, 512, 512, 1024, 1024), vae_layers=(3, 3, 3, 3, 3, 3), weight_seed: int = 0,
+                 vae_chunk: int = 8, synthetic_weights: bool = False, text_encoder_path: Optional[str] = None,
+                 encode_only: bool = False, max_timesteps: float = SCM_MAX_TIMESTEPS,
+                 intermediate_timesteps: Optional[float] = SCM_INTERMEDIATE_TIMESTEPS):
+        if DTYPE not in _ROUND_DTYPES:
+            raise ValueError(f"SanaPipelineES: DTYPE {DTYPE} is not float32, float16 or bfloat16")
+        self.timesteps = scm_timesteps(num_inference_steps, max_timesteps, intermediate_timesteps)
+        self.num_inference_steps = int(num_inference_steps)
+        super().__init__(model_name, device, DTYPE, sigma_data, arch=arch, vae_widths=vae_widths, vae_layers=vae_layers,
+                         weight_seed=weight_seed, vae_chunk=vae_chunk, synthetic_weights=synthetic_weights,
+                         text_encoder_path=text_encoder_path, encode_only=encode_only)
+
+    def _draws(self, b: int, seed: int, h: int, w: int, image_seeds: Optional[Sequence[int]] = None):
+        """(initial latents [b, C, h, w] fp32 x sigma_data, [one fp32 noise per step]) from one generator, in the
+        pipeline's order.  image_seeds: image i has its own generator (its latents, then its step noises)."""
+        C = self.transformer_config.in_channels
+
+        def one(nb, sd):
+            g = torch.Generator(device=self.device).manual_seed(int(sd))
+            shape = (nb, C, h, w)
+            lat = torch.randn(shape, device=self.device, dtype=torch.float32, generator=g) * self.sigma_data
+            return lat, [torch.randn(shape, device=self.device, dtype=torch.float32, generator=g)
+                         for _ in range(self.num_inference_steps)]
+        if image_seeds is None:
+            return one(b, seed)
+        if len(image_seeds) != b:
+            raise ValueError(f"image_seeds has {len(image_seeds)} entries for {b} images")
+        parts = [one(1, s) for s in image_seeds]
+        return (torch.cat([p[0] for p in parts]),
+                [torch.cat([p[1][i] for p in parts]) for i in range(self.num_inference_steps)])
+
+    def _step(self, x, eps, noise, sc: ScmStepScalars, round_dtype: int, members: int, last: bool):
+        """(x_next, m_next, x0_out) of one sampler step, see _step_torch."""
+        if not FUSE_SCM_STEP:
+            return _step_torch(x, eps, noise, sc, round_dtype, members, last)
+        from . import kernels as K
+        new = lambda: torch.empty(eps.shape, dtype=torch.float32, device=eps.device)  # noqa: E731
+        if last:
+            z = new()
+            K.scm_step(x, eps, None, sc, round_dtype, members, x0_out=z)
+            return None, None, z
+        x_next = x if x.numel() == eps.numel() else new()      # every member has its own x by now: in place
+        m_next = new()
+        K.scm_step(x, eps, noise, sc, round_dtype, members, x_next=x_next, m_next=m_next)
+        return x_next, m_next, None
+
+    @torch.no_grad()
+    def _sample(self, draws, prompt_embeds, prompt_attention_mask, guidance_scale, reps: int,
+                prompt_index: Optional[torch.Tensor] = None):
+        """The sampler over reps members of b images: (images [reps * b, 3, H, W], final latents in VAE scale,
+        an NCHW view).  prompt_index: as SanaOneStep._one_step."""
+        lat, noises = draws
+        b, C, h, w = lat.shape
+        rd = _ROUND_DTYPES[self.DTYPE]
+        tm = lambda t: t.permute(0, 2, 3, 1).reshape(b, h * w, C).contiguous()       # noqa: E731  token-major
+        nchw = lambda t: t.view(-1, h, w, C).permute(0, 3, 1, 2)                     # noqa: E731  a view
+        rep = lambda t: t if reps == 1 else t.repeat(reps, *([1] * (t.ndim - 1)))    # noqa: E731  member-major
+        guidance = torch.full((b,), guidance_scale, device=self.device, dtype=self.DTYPE)
+        guidance = rep((guidance * self.transformer_config.guidance_embeds_scale).float())
+        enc_index = None
+        if prompt_index is not None:
+            u = prompt_embeds.shape[0]
+            enc_index = (torch.arange(reps, device=self.device)[:, None] * u
+                         + prompt_index.to(self.device)[None, :]).reshape(-1)
+        pe, am = rep(prompt_embeds), rep(prompt_attention_mask)
+        ts, steps = self.timesteps, self.num_inference_steps
+        x = tm(lat)                                              # [b, hw, C]: shared by every member at step 0
+        in_scale0 = float(torch.tensor(scm_step_scalars(ts[0], ts[1], self.sigma_data).in_scale, dtype=torch.float32))
+        m = rep(_rnd(x * in_scale0, rd))
+        z = None
+        for i in range(steps):
+            last = i == steps - 1
+            sc = scm_step_scalars(ts[i], ts[i + 1], self.sigma_data,
+                                  1.0 / (self.sigma_data * self.vae.scaling_factor) if last else 1.0)
+            s = torch.full((b,), scm_s(ts[i]), device=self.device, dtype=torch.float32).to(self.DTYPE).float()
+            eps = self.transformer(nchw(m), rep(s), pe, am, guidance, enc_index=enc_index)
+            eps = eps.permute(0, 2, 3, 1).reshape(reps * b, h * w, C)   # proj_out's own layout: no copy
+            if not eps.is_contiguous():
+                eps = eps.contiguous()
+            x, m, z = self._step(x, eps, None if last else tm(noises[i]), sc, rd, reps, last)
+        zc = nchw(z)
+        imgs = [self.vae(zc[s:s + self.vae_chunk]) for s in range(0, zc.shape[0], self.vae_chunk)]
+        return torch.cat(imgs), zc
+
+    # ---- reference API (single member: the transformer's own LoRA params) ------------
+    @torch.no_grad()
+    def generate_one_batch(self, prompt_embeds, prompt_attention_mask, seed: int = 0, guidance_scale: float = 1.0,
+                           width_latent: int = 32, height_latent: int = 32, output_type: str = "pil",
+                           image_seeds: Optional[Sequence[int]] = None):
+        """models/SanaSprint.py:458-502: every prompt of the batch in one sampler run; (images, None).
+        image_seeds (build-specific): one generator per image instead of one batched draw from `seed`."""
+        set_population(self.transformer, None)
+        draws = self._draws(prompt_embeds.shape[0], seed, height_latent, width_latent, image_seeds)
+        imgs, _ = self._sample(draws, prompt_embeds.to(self.device), prompt_attention_mask.to(self.device),
+                               guidance_scale, reps=1)
+        return (imgs if output_type == "pt" else to_pil(imgs)), None
+
+    @torch.no_grad()
+    def generate(self, prompt_embeds, prompt_attention_mask, latents=None, seed: int = 0, guidance_scale: float = 1.0,
+                 width_latent: int = 32, height_latent: int = 32, output_type: str = "pil"):
+        """models/SanaSprint.py:431-453: a thin wrapper of generate_one_batch (`latents` is ignored, as there)."""
+        return self.generate_one_batch(prompt_embeds, prompt_attention_mask, seed=seed, guidance_scale=guidance_scale,
+                                       width_latent=width_latent, height_latent=height_latent, output_type=output_type)
+
+    # ---- engine API -----------------------------------------------------------------
+    @torch.no_grad()
+    def generate_population(self, prompt_embeds, prompt_attention_mask, theta_pop: torch.Tensor, seed: int,
+                            guidance_scale: float, width_latent: int, height_latent: int,
+                            prompt_index: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """SanaOneStep.generate_population's contract: all members of theta_pop [n, D] at once, VAE images
+        [n*b, 3, H, W] (member-major); every step's forward uses prompt_index."""
+        n = theta_pop.shape[0]
+        self.ctx.theta_pop, self.ctx.n_members = theta_pop, n
+        set_population(self.transformer, self.ctx)
+        try:
+            b = prompt_embeds.shape[0] if prompt_index is None else prompt_index.numel()
+            imgs, _ = self._sample(self._draws(b, seed, height_latent, width_latent), prompt_embeds,
+                                   prompt_attention_mask, guidance_scale, reps=n, prompt_index=prompt_index)
         finally:
             set_population(self.transformer, None)
             self.ctx.theta_pop = None

@@ -332,6 +332,25 @@ int eggroll_rownorm_ex(const void* x, int32_t x_f32, int64_t rows, int64_t C, fl
  * EPI_RES32 / EPI_GATED32 GEMM epilogues (eggroll_lora_linear_pop_epi epi 4 / 5), bit-identical.   */
 int eggroll_gated_residual_f32(float* x, const void* y, const void* gate, int32_t gate_f32, int64_t gstride,
                                int64_t rows, int64_t C, int64_t rows_per_group, void* shadow, void* stream);
+/* One SCM / trigflow sampler step of the multi-step Sana-Sprint pipeline: everything between transformer
+ * forward i and forward i + 1 (or the decoder) in one elementwise launch.  Per element e of member k
+ * (members of n = b * HW * C elements, token-major), all in fp32:
+ *   m      = rnd(x * in_scale)                  what forward i was fed (one multiply, then the rounding)
+ *   pred   = coef_m * m + coef_eps * rnd(eps)
+ *   x0     = cos_t * x - sin_t * pred
+ *   x_next = cos_n * x0 + sin_n_sd * noise      written if x_next != NULL
+ *   m_next = rnd(x_next * in_scale_next)        written if m_next != NULL (fp32 storage)
+ *   x0_out = x0 * out_scale                     written if x0_out != NULL
+ * x: fp32, member k at x + k * x_member_stride (0: every member reads the same n elements); eps: [members * n]
+ * fp32 (eps_f32 = 1) or bf16; noise: [n] fp32 shared by all members, NULL only when x_next is NULL (the last
+ * step, which wants x0_out alone; noise then counts as 0).  rnd = round_dtype: 0 none,
+ * 1 through fp16, 2 through bf16.  x_next may be x itself when x_member_stride == n.  128-bit accesses when
+ * every pointer is 16-byte aligned (bf16 eps: 8) and n, x_member_stride are multiples of 4 (or members == 1),
+ * with a scalar tail; any n > 0 is valid.  members <= 65535.                                            */
+int eggroll_scm_step(const float* x, int64_t x_member_stride, const void* eps, int32_t eps_f32, const float* noise,
+                     int64_t members, int64_t n, float in_scale, float coef_m, float coef_eps, float cos_t,
+                     float sin_t, float cos_n, float sin_n_sd, float in_scale_next, float out_scale,
+                     int32_t round_dtype, float* x_next, float* m_next, float* x0_out, void* stream);
 /* fp32 residual stream + LayerNorm of the CLIP reward towers (one pass per residual point):
  *   h[r, :] += float(y[r, :])  (y bf16, rows ldy apart; y == NULL: no add, h is only read)
  *   out[r, :] = bf16(layer_norm(h[r, :]) * w + b)   fp32 statistics, w / b bf16 [C], out [rows, C]
