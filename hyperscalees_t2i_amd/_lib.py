@@ -14,7 +14,8 @@ from pathlib import Path
 _PKG = Path(__file__).resolve().parent
 LIB_PATH = _PKG / "_build" / "libeggroll.so"
 HEADER = _PKG.parent / "include" / "eggroll.h"
-SOURCE_FILES = [_PKG / "csrc" / n for n in ("eggroll_es.hip", "eggroll_lora.hip", "eggroll_model.hip", "common.h")] \
+SOURCE_FILES = [_PKG / "csrc" / n for n in ("eggroll_es.hip", "eggroll_lora.hip", "eggroll_model.hip", "eggroll_gguf.hip",
+                                                "common.h")] \
     + [HEADER]
 
 i32, i64, u32, u64, f32 = C.c_int32, C.c_int64, C.c_uint32, C.c_uint64, C.c_float
@@ -99,6 +100,7 @@ SIGNATURES = {
     "eggroll_rope_half": (C.c_int, [vp, i64, i64, i64, i64, i64, vp, vp, vp]),
     "eggroll_causal_attention": (C.c_int, [vp, i64, vp, i64, vp, i64, vp, i64, i64, i64, i64, i64, f32, vp, i64, vp]),
     "eggroll_qk_norm_rope_half": (C.c_int, [vp, i64, i64, i64, i64, i64, i64, f32, vp, vp, vp, vp, vp]),
+    "eggroll_gguf_dequant": (C.c_int, [i32, vp, i64, vp, i32, vp]),
 }
 
 _lib = None

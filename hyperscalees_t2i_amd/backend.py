@@ -447,7 +447,11 @@ class ZImageConfig:
     max_log_batches: int = 1
     compile_transformer: bool = False
     attention_backend: str = "flash"
-    use_gguf: bool = False
+    use_gguf: bool = False                   # the transformer from a GGUF file, dequantised once at load (gguf.py)
+    gguf_repo_id: str = "jayn7/Z-Image-Turbo-GGUF"      # unifed_es.py:476-479; never downloaded from
+    gguf_filename: str = "z_image_turbo-Q3_K_S.gguf"
+    gguf_local_dir: str = "gguf_cache"
+    gguf_local_path: Optional[str] = None
     lora_r: int = 2
     lora_alpha: int = 8
     lora_dropout: float = 0.0
@@ -534,7 +538,10 @@ class ZImageBackend(ESBackend):
         c = self.cfg
         self.es_model = ZImageTurboES(c.model_name, device=self.device, num_inference_steps=c.num_inference_steps,
                                       arch=c.arch or ZIMAGE_TURBO, vae_widths=c.vae_widths, vae_chunk=c.vae_chunk,
-                                      weight_seed=c.weight_seed, synthetic_weights=c.synthetic_weights)
+                                      weight_seed=c.weight_seed, synthetic_weights=c.synthetic_weights,
+                                      use_quantize=c.use_gguf, gguf_repo_id=c.gguf_repo_id,
+                                      gguf_filename=c.gguf_filename, gguf_local_dir=c.gguf_local_dir,
+                                      gguf_local_path=c.gguf_local_path)
         self._load_or_encode_prompts()
         n = attach_lora(self.es_model.transformer, c.lora_r, c.lora_alpha, c.lora_target_modules)
         if n == 0:

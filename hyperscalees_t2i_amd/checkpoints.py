@@ -36,6 +36,7 @@ import json
 from pathlib import Path
 from typing import Callable, Dict, List, Optional, Sequence, Tuple
 
+import numpy as np
 import torch
 from torch import nn
 
@@ -918,3 +919,101 @@ def save_qwen3_encoder(enc, d: Path, prefix: str = "") -> None:
     """The build's Qwen3 weights in transformers' Qwen3Model layout, without the last layer and the final norm
     it never holds (round trips, tools): norm weights in fp32, the rest in bf16."""
     _save_hf_text_encoder(enc, qwen3_rules(enc, prefix), qwen3_config_from_arch(enc.arch), d)
+
+
+# ---------------------------------------------------------------------------------------
+# Z-Image transformer from a GGUF file (gguf.py)
+# ---------------------------------------------------------------------------------------
+# Reference: ZImageTurboES(use_quantize=True, gguf_local_path=...) (models/zImageTurbo.py:76-94,140-193) hands
+# the file to ZImageTransformer2DModel.from_single_file(..., GGUFQuantizationConfig), which keeps the ggml
+# blocks and dequantises in every forward.  Here every tensor is dequantised once, at load, to the bf16
+# weights the build runs on (on the GPU by eggroll_gguf_dequant), then goes through the same strict loader as
+# a safetensors directory.  Files that carry diffusers' parameter names pass through; the single-file (ComfyUI
+# / original checkpoint) names are converted as diffusers' from_single_file does for this model — recalled
+# from diffusers' single_file_utils, UNPINNED like the format itself (no diffusers, no gguf package, no real
+# file offline): PARITY WITH REAL GGUF FILES AND WITH DIFFUSERS' GGUF PATH IS UNPINNED.
+
+ZIMAGE_SINGLE_FILE_PREFIX = "model.diffusion_model."
+_ZIMAGE_SINGLE_FILE_RENAMES = (("final_layer.", "all_final_layer.2-1."), ("x_embedder.", "all_x_embedder.2-1."))
+_ZIMAGE_SINGLE_FILE_ATTN = ((".attention.out.weight", ".attention.to_out.0.weight"),
+                            (".attention.out.bias", ".attention.to_out.0.bias"),
+                            (".attention.q_norm.weight", ".attention.norm_q.weight"),
+                            (".attention.k_norm.weight", ".attention.norm_k.weight"))
+
+
+def read_gguf_state(path, device="cpu") -> Dict[str, torch.Tensor]:
+    """Every tensor of a GGUF file, dequantised one at a time on `device` (F32 / F16 / BF16 keep their dtype,
+    block types become bf16): the peak extra memory is one tensor's raw bytes plus its output."""
+    from . import gguf
+    f = gguf.GGUFFile(path)
+    out: Dict[str, torch.Tensor] = {}
+    for name, (gt, shape, raw) in f.tensors.items():
+        out[name] = gguf.dequantize(raw, gt, shape, device)
+    return out
+
+
+def zimage_gguf_keys_to_diffusers(state: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
+    """Single-file Z-Image names -> diffusers' ZImageTransformer2DModel names (diffusers-named states come back
+    unchanged): the model.diffusion_model. prefix goes, final_layer / x_embedder gain their all_* ModuleDict
+    key "2-1", attention.out / q_norm / k_norm become to_out.0 / norm_q / norm_k, and a fused attention.qkv
+    weight [3 dim, dim] splits into to_q / to_k / to_v (chunk(3, 0), after dequantisation)."""
+    out: Dict[str, torch.Tensor] = {}
+    for k, t in state.items():
+        if k.startswith(ZIMAGE_SINGLE_FILE_PREFIX):
+            k = k[len(ZIMAGE_SINGLE_FILE_PREFIX):]
+        for old, new in _ZIMAGE_SINGLE_FILE_RENAMES:
+            if k.startswith(old):
+                k = new + k[len(old):]
+        for old, new in _ZIMAGE_SINGLE_FILE_ATTN:
+            if k.endswith(old):
+                k = k[:-len(old)] + new
+        if k.endswith(".attention.qkv.weight"):
+            if t.dim() != 2 or t.shape[0] % 3:
+                raise ValueError(f"{k}: a fused qkv weight must be [3 dim, dim], got {tuple(t.shape)}")
+            base = k[:-len("qkv.weight")]
+            for nm, part in zip(("to_q", "to_k", "to_v"), t.chunk(3, dim=0)):
+                out[f"{base}{nm}.weight"] = part
+        else:
+            out[k] = t
+    return out
+
+
+def load_zimage_transformer_gguf(model, path) -> None:
+    """Strict, like load_zimage_transformer: a missing tensor, an unused one or a shape mismatch raises
+    ValueError.  Tensors are dequantised on the model's device."""
+    dev = next(model.parameters()).device
+    state = zimage_gguf_keys_to_diffusers(read_gguf_state(path, dev))
+    load_into(model, zimage_rules(model), state, f"{path} (transformer, GGUF)")
+
+
+def save_zimage_gguf(transformer, path, single_file_names: bool = False) -> None:
+    """The build's frozen Z-Image transformer weights as a GGUF file, for round trips (the K-quantisers are not
+    implemented): 2-D weights whose inner dimension is a multiple of 32 as Q8_0, everything else as F32.
+    single_file_names: the original checkpoint's names (model.diffusion_model. prefix, final_layer /
+    x_embedder, attention.out / q_norm / k_norm) with to_q / to_k / to_v fused into attention.qkv."""
+    from . import gguf
+    state = state_from_build(transformer, zimage_rules(transformer))
+    if single_file_names:
+        named: Dict[str, torch.Tensor] = {}
+        for k, t in state.items():
+            if k.endswith(".attention.to_k.weight") or k.endswith(".attention.to_v.weight"):
+                continue
+            if k.endswith(".attention.to_q.weight"):
+                base = k[:-len("to_q.weight")]
+                k, t = base + "qkv.weight", torch.cat([t, state[base + "to_k.weight"], state[base + "to_v.weight"]], 0)
+            for new, old in _ZIMAGE_SINGLE_FILE_ATTN:
+                if k.endswith(old):
+                    k = k[:-len(old)] + new
+            for new, old in _ZIMAGE_SINGLE_FILE_RENAMES:
+                if k.startswith(old):
+                    k = new + k[len(old):]
+            named[ZIMAGE_SINGLE_FILE_PREFIX + k] = t
+        state = named
+    tensors = {}
+    for k, t in state.items():
+        w = t.detach().float().cpu().contiguous().numpy()
+        if w.ndim == 2 and w.shape[1] % 32 == 0:
+            tensors[k] = (gguf.Q8_0, tuple(w.shape), gguf.quantize_q8_0(w))
+        else:
+            tensors[k] = (gguf.F32, tuple(w.shape), w.reshape(-1).view(np.uint8))
+    gguf.write_gguf(path, tensors, metadata={"general.architecture": "zimage", "general.name": "Z-Image transformer"})

@@ -1327,3 +1327,31 @@ def group_norm_nhwc(x: torch.Tensor, groups: int, w: torch.Tensor, b: torch.Tens
               int(bool(silu)), out.data_ptr(), ws.data_ptr(), _stream(x.device))
     OpTimer.end(e0, f"group_norm(C={C})", 6.0 * x.numel(), f"B{B} HW{HW}")
     return out
+
+
+# ggml type id -> (elements per block, bytes per block) of the block types eggroll_gguf_dequant decodes
+GGUF_BLOCK_TYPES = {2: (32, 18), 3: (32, 20), 6: (32, 22), 7: (32, 24), 8: (32, 34),
+                    10: (256, 84), 11: (256, 110), 12: (256, 144), 13: (256, 176), 14: (256, 210)}
+
+
+def gguf_dequant(raw: torch.Tensor, ggml_type: int, n_elems: int, out_dtype: torch.dtype = torch.bfloat16) -> torch.Tensor:
+    """n_elems values of a ggml block type (Q4_0 / Q4_1 / Q5_0 / Q5_1 / Q8_0 / Q2_K .. Q6_K) from their raw bytes
+    (uint8, on the device, contiguous) -> [n_elems] bf16 (round-to-nearest-even) or fp32: ggml's dequantisation
+    expression with every operation rounded to fp32 (eggroll_gguf_dequant)."""
+    _dev(raw, "gguf_dequant(raw)", torch.uint8)
+    if int(ggml_type) not in GGUF_BLOCK_TYPES:
+        raise ValueError(f"gguf_dequant: ggml type {ggml_type} is not a block type of this kernel "
+                         f"({sorted(GGUF_BLOCK_TYPES)})")
+    if out_dtype not in (torch.bfloat16, torch.float32):
+        raise ValueError(f"gguf_dequant: out_dtype {out_dtype} (bfloat16 or float32)")
+    be, ts = GGUF_BLOCK_TYPES[int(ggml_type)]
+    n = int(n_elems)
+    if n < 0 or n % be or n // be * ts != raw.numel():
+        raise ValueError(f"gguf_dequant: {raw.numel()} bytes for {n} elements of type {ggml_type} "
+                         f"({be} elements per {ts}-byte block)")
+    out = torch.empty(n, dtype=out_dtype, device=raw.device)
+    e0 = OpTimer.begin()
+    _lib.call("eggroll_gguf_dequant", int(ggml_type), raw.data_ptr(), n, out.data_ptr(),
+              int(out_dtype == torch.float32), _stream(raw.device))
+    OpTimer.end(e0, f"gguf_dequant(type={ggml_type})", float(raw.numel() + n * out.element_size()), f"n{n}")
+    return out

@@ -141,12 +141,22 @@ class ZImageTurboES:
                  DTYPE: torch.dtype = torch.bfloat16, num_inference_steps: int = 9, arch: ZImageArch = ZIMAGE_TURBO,
                  vae_widths: Sequence[int] = (128, 256, 512, 512), vae_chunk: int = 16, weight_seed: int = 0,
                  synthetic_weights: bool = False, text_encoder_path: Optional[str] = None,
-                 encode_only: bool = False):
+                 encode_only: bool = False, use_quantize: bool = False,
+                 gguf_repo_id: str = "jayn7/Z-Image-Turbo-GGUF", gguf_filename: str = "z_image_turbo-Q4_K_S.gguf",
+                 gguf_local_dir: str = "gguf_cache", gguf_local_path: Optional[str] = None):
         """text_encoder_path: one local directory with the Qwen3 checkpoint and its tokenizer files, used by
         encode_prompts in place of model_name/text_encoder + model_name/tokenizer.  encode_only: build neither
         the transformer nor the VAE (an instance that exists to call encode_prompts; `arch` then only names
-        the cap_feat_dim the encoder's width is checked against)."""
+        the cap_feat_dim the encoder's width is checked against).  use_quantize (models/zImageTurbo.py:76-94,
+        140-193): the transformer's weights come from a GGUF file, dequantised once at load to bf16 (gguf.py) —
+        gguf_local_path, else gguf_local_dir / gguf_filename; gguf_repo_id is kept for the reference's signature
+        and never downloaded from.  model_name still supplies transformer/config.json (no weights file needed
+        there) and vae/, as the reference takes everything but the transformer from the base model."""
         from . import checkpoints as ck
+        if use_quantize and (synthetic_weights or encode_only):
+            raise ValueError("ZImageTurboES: use_quantize=True loads the transformer from a GGUF file; it cannot be "
+                             f"combined with {'synthetic_weights' if synthetic_weights else 'encode_only'}=True")
+        self.use_quantize, self.gguf_repo_id, self.gguf_path = bool(use_quantize), gguf_repo_id, None
         self.model_name, self.device, self.DTYPE = model_name, device, torch.bfloat16
         self.num_inference_steps = int(num_inference_steps)
         self.text_encoder_path = str(text_encoder_path) if text_encoder_path else None
@@ -167,21 +177,42 @@ class ZImageTurboES:
             # ZImagePipeline.from_pretrained(model_name) (models/zImageTurbo.py:97-125): a LOCAL diffusers
             # directory (transformer/ + vae/, checkpoints.py); no hub access offline
             root = Path(model_name)
+            if use_quantize:   # resolved first: a wrong GGUF path is reported before anything is built
+                self.gguf_path = self._resolve_gguf(gguf_local_path, gguf_local_dir, gguf_filename, gguf_repo_id)
             if not (root / "transformer").is_dir() or not (root / "vae").is_dir():
                 raise FileNotFoundError(f"{model_name}: not a local diffusers Z-Image directory (transformer/ + vae/); "
                                         "pass synthetic_weights=True for the throughput configuration")
             self.arch = ck.zimage_arch_from_config(ck.read_config(root / "transformer"))
             self.transformer = ZImageTransformer2DModel(self.arch).to(device)
-            ck.load_zimage_transformer(self.transformer, root / "transformer")
+            if use_quantize:
+                from .gguf import GGUFFile
+                ck.load_zimage_transformer_gguf(self.transformer, self.gguf_path)
+                counts = ", ".join(f"{k}\u00d7{v}" for k, v in GGUFFile(self.gguf_path).type_counts().items())
+            else:
+                ck.load_zimage_transformer(self.transformer, root / "transformer")
             vk = ck.flux_vae_kwargs(ck.read_config(root / "vae"))
             vae_widths = vk["widths"]
             self.vae = FluxVAEDecoder(**vk).to(device)
             ck.load_flux_vae_decoder(self.vae, root / "vae")
-            self.weights_source = str(root)
+            self.weights_source = f"{self.gguf_path} (GGUF: {counts}); vae: {root}" if use_quantize else str(root)
         self.vae_chunk = vae_chunk
         self.vae_scale_factor = 2 ** (len(vae_widths) - 1)
         self.ctx = PopulationContext()
         self.vae_ctx = PopulationContext()   # theta rows of the decoding members when the VAE decoder has LoRA
+
+    @staticmethod
+    def _resolve_gguf(local_path, local_dir, filename, repo_id) -> Path:
+        """models/zImageTurbo.py:140-160 without the hub: gguf_local_path wins, else gguf_local_dir / gguf_filename
+        if that file exists; nothing is ever downloaded."""
+        cached = Path(str(local_dir)) / str(filename)
+        if local_path:
+            if Path(str(local_path)).is_file():
+                return Path(str(local_path))
+        elif cached.is_file():
+            return cached
+        raise FileNotFoundError(f"Z-Image GGUF file not found: gguf_local_path={str(local_path) if local_path else None!r}, "
+                                f"gguf_local_dir/gguf_filename={str(cached)!r}; there is no hub access, so "
+                                f"{repo_id!r} is not downloaded — place the file at one of these paths")
 
     # ---- prompt cache (models/zImageTurbo.py:226-309) -------------------------------
     def encode_prompts(self, prompts_txt_path, encoded_save_path, batch_size: int = 64, max_sequence_length: int = 512,

@@ -558,6 +558,20 @@ int eggroll_qk_norm_rope_half(void* x, int64_t ldx, int64_t B, int64_t N, int64_
                               int64_t head_dim, float eps, const float* wq, const float* wk, const float* cos_t,
                               const float* sin_t, void* stream);
 
+/* GGUF block dequantisation (the load-time path of a GGUF-quantised Z-Image transformer, gguf.py):
+ * blocks: n_elems / block_elems(type) consecutive ggml blocks of `ggml_type` in device memory, at least 2-byte
+ * aligned (16-byte aligned, as a tensor base is, takes the wide-load path).  The ten block types:
+ *   Q4_0 2, Q4_1 3, Q5_0 6, Q5_1 7, Q8_0 8 (32 elements in 18 / 20 / 22 / 24 / 34 bytes) and
+ *   Q2_K 10, Q3_K 11, Q4_K 12, Q5_K 13, Q6_K 14 (256 elements in 84 / 110 / 144 / 176 / 210 bytes).
+ * out: n_elems values, 16-byte aligned, bf16 (out_fp32 == 0, round-to-nearest-even) or fp32 (out_fp32 == 1).
+ * The fp32 value is ggml's dequantisation expression of the type with every multiply / add / subtract rounded
+ * to fp32 on its own (no FMA), fp16 fields widened exactly; bf16 is the rounding of that value.  No byte past
+ * n_blocks * type_size is read and nothing past n_elems outputs is written.  One launch, n_elems <= 2^31.
+ * Returns 0; -1 with eggroll_last_error() naming "gguf_dequant" for an unsupported type, n_elems < 0 or not a
+ * multiple of the block size, or a null pointer with n_elems > 0.  n_elems == 0 is a no-op returning 0. */
+int eggroll_gguf_dequant(int32_t ggml_type, const void* blocks, int64_t n_elems, void* out, int32_t out_fp32,
+                         void* stream);
+
 #ifdef __cplusplus
 }
 #endif
