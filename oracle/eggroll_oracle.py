@@ -398,3 +398,135 @@ def ref_lora_linear_pop(x: np.ndarray, W: np.ndarray, bias, theta_pop: np.ndarra
         B = theta_pop[k, offB:offB + N * r].reshape(N, r)
         out[sl] = ref_lora_linear(x[sl], W, bias, A, B, scale)
     return out
+
+
+# ---------------------------------------------------------------------------------------
+# Large-population / edge-case helpers (tests/test_es_edges.py, tests/test_gpu_es_edges.py)
+# ---------------------------------------------------------------------------------------
+
+
+def _seq_sum(x: np.ndarray, axis: int) -> np.ndarray:
+    """The kernels' `acc = 0; for i: acc = acc + x[i]` in fp32 along `axis`, vectorised over the other
+    axes: np.add.accumulate is a left fold (it has to produce every prefix).  The trailing `+ 0` restates
+    the loop's start from +0.0 (a fold over nothing but -0.0 is -0.0, the loop's result +0.0)."""
+    x = np.asarray(x, F32)
+    if x.shape[axis] == 0:
+        return np.zeros(np.delete(x.shape, axis), F32)
+    return (np.take(np.add.accumulate(x, axis=axis, dtype=F32), -1, axis=axis) + F32(0)).astype(F32)
+
+
+def dev_fitness_fast(S: np.ndarray, promptnorm: bool, eps: float = 1e-8):
+    """dev_fitness with every loop over members / prompts vectorised (same fp32 values in the same
+    sequential order; tests/test_es_edges.py pins it bit-identical to the loop form)."""
+    S = np.asarray(S, F32)
+    n, m = S.shape
+    with np.errstate(all="ignore"):
+        mu = (_seq_sum(S, 0) / F32(n)).astype(F32)
+        sigma_bar = F32(np.nan)
+        if promptnorm:
+            c = (S - mu[None, :]).astype(F32)
+            ss = _seq_sum(_seq_sum((c * c).astype(F32), 1), 0)
+            sb = F32(np.sqrt(F32(ss / F32(n * m))))
+            if sb < F32(eps):
+                sb = F32(eps)
+            sigma_bar = sb
+            sc = (_seq_sum((c / sb).astype(F32), 1) / F32(m)).astype(F32)
+        else:
+            sc = (_seq_sum(S, 1) / F32(m)).astype(F32)
+        fin = np.isfinite(sc)
+        nf = int(fin.sum())
+        mean = F32(_seq_sum(sc[fin], 0) / F32(nf))
+        d = (sc[fin] - mean).astype(F32)
+        sq = _seq_sum((d * d).astype(F32), 0)
+        std = F32(np.sqrt(F32(sq / F32(nf - 1))))
+        f = np.zeros(n, F32)
+        if not bool(std < F32(1e-8)):
+            f[fin] = (d / F32(std + F32(1e-8))).astype(F32)
+    order = np.argsort(sc, kind="stable").astype(np.int32)      # NaN last, ties (and -0 / +0) in index order
+    stats = np.array([sigma_bar, nf, mean, std], F32)
+    return {"scores": sc, "mu": mu, "stats": stats, "fitness": f, "finite": fin.astype(np.int32), "order": order}
+
+
+def collapse_fitness(fit: np.ndarray, pop: int, antithetic: bool, dtype=np.float64) -> np.ndarray:
+    """Per-base-sample coefficient of the update: c_j = f_j - f_{j+h} (antithetic pairs), the unpaired
+    last member of an odd population c_h = f_{2h}; f_j without antithetic sampling.  Each difference is
+    rounded to `dtype` (fp32 restates k_update)."""
+    f = np.asarray(fit).astype(dtype)
+    if not antithetic:
+        return f[:pop].copy()
+    h = pop // 2
+    c = np.zeros(n_base_samples(pop, True), dtype)
+    c[:h] = f[:h] - f[h:2 * h]
+    if pop % 2:
+        c[h] = f[2 * h]
+    return c
+
+
+def ref_update_f64(theta: np.ndarray, factors: np.ndarray, shapes, fit: np.ndarray, nf: int, pop: int, rank: int,
+                   antithetic: bool, lr: float):
+    """The update from the fp32 factors (reference order, [>= n_base, factor_len_packed]) and the fp32
+    fitness vector, evaluated in fp64: G[d] = sum_j c_j E_j[d], ref = theta + lr G / N_f (theta when no
+    member is finite).  Also returns A[d] = sum_j |c_j| sum_q |a b| / sqrt(r), the magnitude that scales
+    the fp32 summation error (update_bound)."""
+    nb = n_base_samples(pop, antithetic)
+    c = collapse_fitness(fit, pop, antithetic)
+    ca = np.abs(c)
+    blocks = split_factors(np.asarray(factors, F32)[:nb].astype(np.float64), shapes, rank)
+    sr = math.sqrt(rank)
+    G, A = [], []
+    for blk, s in zip(blocks, shapes):
+        if len(s) == 2:
+            a, b = blk
+            G.append((np.einsum("j,jiq,jcq->ic", c, a, b) / sr).reshape(-1))
+            A.append((np.einsum("j,jiq,jcq->ic", ca, np.abs(a), np.abs(b)) / sr).reshape(-1))
+        else:
+            G.append(c @ blk)
+            A.append(ca @ np.abs(blk))
+    G, A = np.concatenate(G), np.concatenate(A)
+    th = np.asarray(theta, F32).astype(np.float64)
+    ref = th + float(lr) * G / nf if nf > 0 else th.copy()
+    return ref, A
+
+
+def update_bound(ref: np.ndarray, A: np.ndarray, n_base: int, rank: int, lr: float, nf: int) -> np.ndarray:
+    """|fp32 update - ref_update_f64| element by element, from sequential fp32 summation (u = 2^-24): r
+    products, r - 1 adds, the division by the rounded sqrt(r) (r + 2 roundings of eps), the rounding of
+    c_j, of c_j * eps_j, n_base - 1 adds of partial sums no larger than A, the division by N_f and the
+    product with lr: (n_base + r + 5) u lr A / N_f to first order, stated with + 6; the final add rounds
+    theta' once (u |ref|, stated as 2 u |ref|)."""
+    return (n_base + rank + 6) * 2.0 ** -24 * float(lr) * A / max(nf, 1) + 2.0 ** -23 * np.abs(ref)
+
+
+def ref_caps_f64(theta: np.ndarray, after: np.ndarray, max_step_norm: float, theta_max_norm: float):
+    """cap_step_norm then cap_theta_norm (utills.py:333-349) in fp64.  Returns (theta', step scale, theta
+    scale); a scale is 1.0 where its cap does not trigger."""
+    th = np.asarray(theta).astype(np.float64)
+    after = np.asarray(after).astype(np.float64)
+    ss = ts = 1.0
+    if max_step_norm and max_step_norm > 0:
+        d = after - th
+        dn = float(np.linalg.norm(d))
+        if dn > max_step_norm:
+            ss = max_step_norm / (dn + 1e-8)
+            after = th + d * ss
+    if theta_max_norm and theta_max_norm > 0:
+        n = float(np.linalg.norm(after))
+        if n > theta_max_norm:
+            ts = theta_max_norm / (n + 1e-8)
+            after = after * ts
+    return after, ss, ts
+
+
+def dev_update_generic(theta: np.ndarray, factors: np.ndarray, shapes, fit: np.ndarray, nf: int, pop: int,
+                       rank: int, antithetic: bool, lr: float) -> np.ndarray:
+    """fp32 emulation of the update in the generic per-element op order (update_chunk): eps_j as
+    dev_eps_rows, acc = acc + c_j * eps_j over base samples j = 0, 1, ..., then theta + lr * (acc / N_f)."""
+    nb = n_base_samples(pop, antithetic)
+    c = collapse_fitness(np.asarray(fit, F32), pop, antithetic, F32)
+    E = dev_eps_rows(np.asarray(factors, F32), shapes, nb, rank, False, 0, nb)
+    th = np.asarray(theta, F32)
+    if nf <= 0:
+        return th.copy()
+    acc = _seq_sum((c[:, None] * E).astype(F32), 0)
+    g = (acc / F32(nf)).astype(F32)
+    return (th + (F32(lr) * g).astype(F32)).astype(F32)
