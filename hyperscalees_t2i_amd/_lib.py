@@ -14,9 +14,10 @@ from pathlib import Path
 _PKG = Path(__file__).resolve().parent
 LIB_PATH = _PKG / "_build" / "libeggroll.so"
 HEADER = _PKG.parent / "include" / "eggroll.h"
-SOURCE_FILES = [_PKG / "csrc" / n for n in ("eggroll_es.hip", "eggroll_lora.hip", "eggroll_model.hip", "eggroll_gguf.hip",
-                                                "common.h")] \
-    + [HEADER]
+from .build_ext import SOURCES  # noqa: E402  (build_ext imports this module only inside its functions)
+
+# everything the library is built from: the translation units, every csrc header, the public header
+SOURCE_FILES = [_PKG / "csrc" / n for n in SOURCES] + sorted((_PKG / "csrc").glob("*.h")) + [HEADER]
 
 i32, i64, u32, u64, f32 = C.c_int32, C.c_int64, C.c_uint32, C.c_uint64, C.c_float
 vp = C.c_void_p

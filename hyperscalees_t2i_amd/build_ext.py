@@ -16,7 +16,8 @@ ROOT = PKG.parent
 CSRC = PKG / "csrc"
 BUILD = PKG / "_build"
 LIB = BUILD / "libeggroll.so"
-SOURCES = ["eggroll_es.hip", "eggroll_lora.hip", "eggroll_model.hip", "eggroll_gguf.hip"]
+# the translation units of libeggroll: the one list (_lib.SOURCE_FILES and the tools derive theirs from it)
+SOURCES = ["eggroll_es.hip", "eggroll_lora.hip", "eggroll_conv.hip", "eggroll_model.hip", "eggroll_gguf.hip"]
 ARCH = "gfx950"
 
 

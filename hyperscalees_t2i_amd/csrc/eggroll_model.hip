@@ -591,7 +591,7 @@ __global__ __launch_bounds__(256) void k_gated_residual(unsigned short* __restri
 // fp32 residual stream update (Sana blocks):  x[r, c] = fma(gate[g, c], y[r, c], x[r, c])
 // (x fp32 in place, y bf16, gate bf16 or fp32 (g32) or NULL = 1: x += y), optionally also writing the
 // bf16 shadow copy of x that the next GEMM reads.  The same expression as the fused GEMM epilogues
-// EPI_RES32 / EPI_GATED32 of eggroll_lora.hip, so fused == unfused bit for bit.
+// EPI_RES32 / EPI_GATED32 of p8_epilogue.h, so fused == unfused bit for bit.
 __global__ __launch_bounds__(256) void k_gated_residual_f32(float* __restrict__ x, const unsigned short* __restrict__ y,
                                                             const void* __restrict__ gate, int g32, int64_t gstride,
                                                             int64_t rows_per_group, int C, int64_t total_chunks,

@@ -306,6 +306,8 @@ def gemm_tile(request):
     (512, 96, 192, 4, 128),       # r = 4 (VAR-like lora rank)
     (64, 32, 2240, 2, 16),        # proj_out-like N = 32, time-embed rows per member = 16
     (1536, 320, 512, 1, 700),     # r = 1, tiles straddling two members (MFMA epilogue member blocks)
+    (513, 330, 128, 2, 300),      # two K-tiles on the MFMA-addend path (the shortest even trip of the 8-phase
+                                  # loop), ragged last column tile for 256 and 320, a one-row third row tile
 ])
 def test_lora_linear_pop_vs_fp64(dev, gemm_tile, M, N, Kd, r, rpm):
     x, W, b, tp, offA, offB = _lora_case(dev, M, N, Kd, r, rpm)

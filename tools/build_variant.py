@@ -7,7 +7,8 @@ from concurrent.futures import ThreadPoolExecutor
 from pathlib import Path
 
 ROOT = Path(__file__).resolve().parent.parent
-SRCS = ["eggroll_es.hip", "eggroll_lora.hip", "eggroll_model.hip"]
+sys.path.insert(0, str(ROOT))
+from hyperscalees_t2i_amd.build_ext import SOURCES as SRCS  # noqa: E402
 
 
 def main(name, flags):
@@ -20,7 +21,7 @@ def main(name, flags):
                         f"-I{ROOT / 'include'}", str(ROOT / "hyperscalees_t2i_amd" / "csrc" / s), "-o", str(o)],
                        check=True, capture_output=True)
         return str(o)
-    with ThreadPoolExecutor(3) as ex:
+    with ThreadPoolExecutor(len(SRCS)) as ex:
         objs = list(ex.map(cc, SRCS))
     subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-shared", "-fPIC", *objs, "-o", str(out)], check=True)
     for o in objs:

@@ -17,7 +17,9 @@ OUT = ROOT / "tools" / "_ab" / "libeggroll_stamps.so"   # travels to the GPU box
 def build():
     OUT.parent.mkdir(parents=True, exist_ok=True)
     objs = []
-    for src in ["eggroll_es.hip", "eggroll_lora.hip", "eggroll_model.hip"]:
+    sys.path.insert(0, str(ROOT))
+    from hyperscalees_t2i_amd.build_ext import SOURCES
+    for src in SOURCES:
         o = OUT.parent / (Path(src).stem + "_stamps.o")
         subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-c",
                         "-DEGG_STAMPS", f"-I{ROOT / 'include'}", str(ROOT / "hyperscalees_t2i_amd" / "csrc" / src),
@@ -33,7 +35,7 @@ def main():
     sys.path.insert(0, str(ROOT))
     from hyperscalees_t2i_amd import kernels as K
     lib = ctypes.CDLL(str(OUT))
-    lib.eggroll_debug_stamps.argtypes = [ctypes.c_void_p, ctypes.c_int64]
+    lib.eggroll_debug_conv_stamps.argtypes = [ctypes.c_void_p, ctypes.c_int64]
     dev = torch.device("cuda:0")
     st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
     vp, i64, i32 = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32
@@ -51,7 +53,7 @@ def main():
                                                  st) == 0
             torch.cuda.synchronize()
             buf = np.zeros(nblk * 8, dtype=np.uint64)
-            assert lib.eggroll_debug_stamps(buf.ctypes.data, buf.size) == 0
+            assert lib.eggroll_debug_conv_stamps(buf.ctypes.data, buf.size) == 0
             s = buf.reshape(nblk, 8).astype(np.int64)
             clk = np.median((s[:, 5] - s[:, 0]) / np.maximum(s[:, 7] - s[:, 6], 1) * 100e6)
             med = lambda v: int(np.median(v))  # noqa: E731

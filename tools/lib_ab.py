@@ -12,7 +12,6 @@ import tempfile
 from pathlib import Path
 
 ROOT = Path(__file__).resolve().parent.parent
-SRCS = ["eggroll_es.hip", "eggroll_lora.hip", "eggroll_model.hip"]
 
 
 def build_a(rev):
@@ -23,8 +22,7 @@ def build_a(rev):
                              capture_output=True).stdout
         subprocess.run(["tar", "-x", "-C", td], input=arc, check=True)
         objs = []
-        for s in SRCS:
-            src = Path(td) / "hyperscalees_t2i_amd" / "csrc" / s
+        for src in sorted((Path(td) / "hyperscalees_t2i_amd" / "csrc").glob("*.hip")):  # the revision's own file set
             o = Path(td) / (src.stem + ".o")
             subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-c",
                             f"-I{Path(td) / 'include'}", str(src), "-o", str(o)], check=True)

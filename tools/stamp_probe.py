@@ -1,5 +1,5 @@
 """Where a tile's time goes in the 8-phase kernels: per-workgroup s_memtime stamps from a
-diagnostic build of eggroll_lora.hip (-DEGG_STAMPS; tools/_stamps/libeggroll_stamps.so, built
+diagnostic build of the library (-DEGG_STAMPS; tools/_stamps/libeggroll_stamps.so, built
 here with `python tools/stamp_probe.py build`, never loaded by the package).
 
 Stamps (wave 0 of each workgroup): 0 start, 1 prologue landed (first barrier), 2 main loop done,
@@ -20,7 +20,8 @@ OUT = ROOT / "tools" / "_stamplib" / "libeggroll_stamps.so"  # build only for a 
 
 def build():
     OUT.parent.mkdir(parents=True, exist_ok=True)
-    srcs = ["eggroll_es.hip", "eggroll_lora.hip", "eggroll_model.hip"]
+    sys.path.insert(0, str(ROOT))
+    from hyperscalees_t2i_amd.build_ext import SOURCES as srcs
     objs = []
     for s in srcs:
         o = OUT.parent / (Path(s).stem + "_stamps.o")
