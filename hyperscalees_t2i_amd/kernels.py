@@ -1174,7 +1174,7 @@ def flash_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: fl
     return out
 
 
-RELBIAS_MAX_N = 512   # RB_NMAX in eggroll_model.hip
+RELBIAS_MAX_N = 512   # RB_NMAX in csrc/eggroll_attn.hip
 
 
 def _seq_attention(name: str, head_dim: int, q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, lens: torch.Tensor,

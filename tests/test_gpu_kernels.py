@@ -1493,12 +1493,20 @@ def test_dcae_high_res_chunking_is_exact(dev, fp32_stages):
     assert (got.float() - want.float()).abs().max().item() < 3e-2
 
 
-@pytest.mark.parametrize("B,Nq,Lk,H,strided", [(2, 676, 676, 3, False), (3, 1, 1, 2, False), (2, 100, 2521, 2, True),
-                                               (1, 257, 130, 1, True), (4, 64, 64, 2, False)])
-def test_flash_attention_vs_sdpa(dev, B, Nq, Lk, H, strided):
+_FLASH_CASES = [(2, 676, 676, 3, False), (3, 1, 1, 2, False), (2, 100, 2521, 2, True), (1, 257, 130, 1, True),
+                (4, 64, 64, 2, False)]
+# every query-fragment count of the kernel (qf 0 = the default, 2): a ragged query block at 64, 128 and 256 queries
+# per workgroup with a partial last key block, and fewer queries than one 256-query block
+_FLASH_QF_CASES = [(1, 257, 130, 1, True, 1), (1, 257, 130, 1, True, 4),
+                   (2, 100, 200, 2, False, 0), (2, 100, 200, 2, False, 1), (2, 100, 200, 2, False, 4)]
+
+
+@pytest.mark.parametrize("B,Nq,Lk,H,strided,qf",
+                         [pytest.param(*c, 0, id="-".join(str(x) for x in c)) for c in _FLASH_CASES] + _FLASH_QF_CASES)
+def test_flash_attention_vs_sdpa(dev, B, Nq, Lk, H, strided, qf):
     """eggroll_flash_attention (head dim 128, online softmax over 64-key blocks, P in bf16 for the PV MFMA) vs
     fp32 SDPA on the same bf16 inputs; k / v optionally a slice of a longer [B, ltot, H*128] cache (batch
-    stride != rows * row stride), ragged query / key counts."""
+    stride != rows * row stride), ragged query / key counts; qf: 16-query fragments per wave (0 = default)."""
     g = torch.Generator(device=dev).manual_seed(Nq * 7 + Lk)
     q = (torch.randn(B, Nq, H, 128, generator=g, device=dev) * 0.3).bfloat16()
     if strided:
@@ -1509,7 +1517,7 @@ def test_flash_attention_vs_sdpa(dev, B, Nq, Lk, H, strided):
         k = (torch.randn(B, Lk, H, 128, generator=g, device=dev) * 0.3).bfloat16()
         v = torch.randn(B, Lk, H, 128, generator=g, device=dev).bfloat16()
     scale = 128 ** -0.5 * 3
-    got = K.flash_attention(q, k, v, scale).float()
+    got = K.flash_attention(q, k, v, scale, qf=qf).float()
     ref = torch.nn.functional.scaled_dot_product_attention(q.float().transpose(1, 2), k.float().transpose(1, 2),
                                                            v.float().transpose(1, 2), scale=scale).transpose(1, 2)
     err = ((got - ref).norm() / ref.norm()).item()

@@ -20,7 +20,8 @@ ALLOWED = re.compile(r"^_ZN7eggroll8k_update")
 
 
 @pytest.mark.skipif(not isa_scan.tools_present(), reason="ROCm LLVM tools absent")
-@pytest.mark.parametrize("unit", ["eggroll_es", "eggroll_lora", "eggroll_conv", "eggroll_model"])
+@pytest.mark.parametrize("unit", ["eggroll_es", "eggroll_lora", "eggroll_conv", "eggroll_model",
+                                  "eggroll_attn"])
 def test_no_unguarded_scalar_data_loads(unit):
     obj = BUILD / f"{unit}.o"
     if not obj.exists():

@@ -23,9 +23,9 @@ NOTES = {"vgpr": ".vgpr_count", "agpr": ".agpr_count", "sgpr": ".sgpr_count", "v
          "sgpr_spill": ".sgpr_spill_count", "private_segment": ".private_segment_fixed_size",
          "lds": ".group_segment_fixed_size"}
 
-# old demangled kernel name -> its name after the 8-phase LoRA kernels became one template
-RENAMES = [(re.compile(r"k_lora_gemm8n<(\d+), (\d+)>"), r"k_lora_gemm8<eggroll::G8<2, 5>, \1, true, \2>"),
-           (re.compile(r"k_lora_gemm8<(\d+), (true|false), (\d+)>"), r"k_lora_gemm8<eggroll::G8<2, 4>, \1, \2, \3>")]
+# (pattern, replacement) pairs: old demangled kernel name -> its new name.  The attention kernels kept their names
+# when they moved to eggroll_attn.hip, so the table is empty.
+RENAMES = []
 
 
 def demangle(names):
