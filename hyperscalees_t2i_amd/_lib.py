@@ -94,6 +94,9 @@ SIGNATURES = {
                                              i64, i32, vp]),
     "eggroll_clip_preprocess": (C.c_int, [vp, i64, i64, i64, i64, i64, i64, i64, i32, vp, vp, i32, i32, i64, i64,
                                           i64, vp, vp, vp, vp, vp]),
+    "eggroll_clip_preprocess_u8": (C.c_int, [vp, i64, i64, i64, i64, i64, i64, i64, vp, vp, i32, i32, i64, i64, i64,
+                                             vp, vp, vp, vp, vp]),
+    "eggroll_images_to_u8": (C.c_int, [vp, i64, i64, i64, i64, i64, i64, i64, i32, vp, vp]),
     "eggroll_relbias_attention": (C.c_int, [vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, i64, i64, i64, f32, vp, i64,
                                             vp]),
     "eggroll_softcap_attention": (C.c_int, [vp, i64, vp, i64, vp, i64, vp, i64, i64, i64, i64, i64, f32, f32, vp, i64,

@@ -249,15 +249,23 @@ class SanaBackend(ESBackend):
         return images
 
     def generate_population(self, flat_ids: List[int], seed: int, guidance_scale: float,
-                            theta_pop: torch.Tensor) -> torch.Tensor:
+                            theta_pop: torch.Tensor, flat_seeds: Optional[List[int]] = None) -> torch.Tensor:
         """flat_ids repeats each sampled prompt batches_per_gen times (repeat_batches): the distinct
         prompts are gathered once and every image points at its prompt's row, so the caption path
-        (caption projection, to_k / to_v of every block) runs on m instead of m*R captions per member."""
+        (caption projection, to_k / to_v of every block) runs on m instead of m*R captions per member.
+        flat_seeds (evaluation): as generate_flat's, image i of every member draws from Generator(flat_seeds[i])
+        instead of the one batched draw from `seed`."""
         uniq = list(dict.fromkeys(int(f) for f in flat_ids))
         idx = torch.tensor([uniq.index(int(f)) for f in flat_ids], device=self.device)
         pe, am = self._gather(uniq)
+        if flat_seeds is None:
+            return self.es_model.generate_population(pe, am, theta_pop, seed, guidance_scale, self.cfg.width_latent,
+                                                     self.cfg.height_latent, prompt_index=idx)
+        if len(flat_seeds) != len(flat_ids):
+            raise ValueError(f"flat_seeds has {len(flat_seeds)} entries, flat_ids {len(flat_ids)}")
         return self.es_model.generate_population(pe, am, theta_pop, seed, guidance_scale, self.cfg.width_latent,
-                                                 self.cfg.height_latent, prompt_index=idx)
+                                                 self.cfg.height_latent, prompt_index=idx,
+                                                 flat_seeds=[int(s) for s in flat_seeds])
 
     def members_per_pass(self) -> Optional[int]:
         return self.cfg.members_per_pass or None

@@ -817,6 +817,23 @@ def scm_step(x: torch.Tensor, eps: torch.Tensor, noise: Optional[torch.Tensor], 
                                       + 4 * nout * members * n), f"n{n}x{members}")
 
 
+def images_to_u8(images: torch.Tensor, pil_mode: int = 0) -> torch.Tensor:
+    """Decoder images [n, 3, H, W] (bf16, any strides) -> the bytes of their PIL "RGB" images, uint8 [n, H, W, 3]
+    on the device (eggroll_images_to_u8).  pil_mode: the backend's conversion, as rewards.clip_pixels (0 PixArt
+    postprocess, rounding; 1 the VAR path, fp16 + truncation; 2 Infinity's, bf16 + truncation)."""
+    _dev(images, "images_to_u8(images)", torch.bfloat16, contiguous=False)
+    if images.ndim != 4 or images.shape[1] != 3:
+        raise _lib.EggrollError(f"images_to_u8: expected [n, 3, H, W], got {tuple(images.shape)}")
+    n, _, h, w = images.shape
+    out = torch.empty((n, h, w, 3), dtype=torch.uint8, device=images.device)
+    sn, sc, sh, sw = images.stride()
+    e0 = OpTimer.begin()
+    _lib.call("eggroll_images_to_u8", images.data_ptr(), n, h, w, sn, sc, sh, sw, int(pil_mode), out.data_ptr(),
+              _stream(images.device))
+    OpTimer.end(e0, "images_to_u8", 9.0 * n * h * w, f"{n}x{h}x{w}")
+    return out
+
+
 def resid_layernorm_(h: torch.Tensor, y: Optional[torch.Tensor], w: torch.Tensor, b: torch.Tensor, eps: float,
                      out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """h [..., C] fp32 (rows may be strided: a [n, T, C] stream or its [:, 0] rows) += y (bf16, same row

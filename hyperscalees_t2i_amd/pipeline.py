@@ -129,6 +129,13 @@ class GemmaPromptEncoder:
         if not prompts:
             raise ValueError(f"{prompts_txt_path}: no prompts (blank {'lines' if keep_comments else 'and # lines'} "
                              f"are skipped)")
+        return self.encode_list(prompts, encoded_save_path, batch_size, complex_human_instruction)
+
+    @torch.no_grad()
+    def encode_list(self, prompts: Sequence[str], encoded_save_path, batch_size: int = 4,
+                    complex_human_instruction=None) -> dict:
+        """encode_file's payload for the given prompts, in their order, none dropped."""
+        prompts = [str(p) for p in prompts]
         embeds, masks = [], []
         for start in range(0, len(prompts), max(int(batch_size), 1)):
             e, m = self.encode(self.preprocess(prompts[start:start + max(int(batch_size), 1)]),
@@ -240,6 +247,16 @@ class _SanaStack(ESBaseModel):
         return self._prompt_encoder.encode_file(prompts_txt_path, enc, batch_size, complex_human_instruction,
                                                 self.KEEP_COMMENT_PROMPTS)
 
+    def encode_prompt_list(self, prompts: Sequence[str], encoded_save_path, batch_size: int = 4,
+                           complex_human_instruction=None):
+        """encode_prompts for prompts given as a list (a prompt table's column): every entry is encoded, in order,
+        so row i of the file is prompts[i].  Always writes encoded_save_path."""
+        if self._prompt_encoder is None or self._prompt_encoder.encoder is None:
+            cc = self.transformer_config.caption_channels if self.transformer is not None else None
+            self._prompt_encoder = GemmaPromptEncoder(self.model_name, self.device, self.text_encoder_path, cc)
+            self.tokenizer, self.text_encoder = self._prompt_encoder.tokenizer, self._prompt_encoder.encoder
+        return self._prompt_encoder.encode_list(prompts, Path(encoded_save_path), batch_size, complex_human_instruction)
+
     def drop_text_encoder(self):
         if self._prompt_encoder is not None:
             self._prompt_encoder.drop()
@@ -310,15 +327,23 @@ class SanaOneStep(_SanaStack):
     @torch.no_grad()
     def generate_population(self, prompt_embeds, prompt_attention_mask, theta_pop: torch.Tensor, seed: int,
                             guidance_scale: float, width_latent: int, height_latent: int,
-                            prompt_index: Optional[torch.Tensor] = None) -> torch.Tensor:
+                            prompt_index: Optional[torch.Tensor] = None,
+                            flat_seeds: Optional[Sequence[int]] = None) -> torch.Tensor:
         """All members of theta_pop [n, D] at once: returns VAE images [n*b, 3, H, W] (member-major).
-        prompt_index: [b] image -> distinct-prompt row (prompt_embeds then holds the distinct prompts)."""
+        prompt_index: [b] image -> distinct-prompt row (prompt_embeds then holds the distinct prompts).
+        flat_seeds: [b] per-image seeds: image i gets the latents of a one-image draw from Generator(flat_seeds[i])
+        (every member the same ones) instead of its slice of one b-image draw from `seed`."""
         n = theta_pop.shape[0]
         self.ctx.theta_pop, self.ctx.n_members = theta_pop, n
         set_population(self.transformer, self.ctx)
         try:
             b = prompt_embeds.shape[0] if prompt_index is None else prompt_index.numel()
-            latents = self._latents(b, seed, height_latent, width_latent)
+            if flat_seeds is None:
+                latents = self._latents(b, seed, height_latent, width_latent)
+            else:
+                if len(flat_seeds) != b:
+                    raise ValueError(f"flat_seeds has {len(flat_seeds)} entries for {b} images")
+                latents = torch.cat([self._latents(1, int(s), height_latent, width_latent) for s in flat_seeds])
             imgs, _ = self._one_step(latents, prompt_embeds, prompt_attention_mask, guidance_scale, reps=n,
                                      prompt_index=prompt_index)
         finally:
@@ -537,15 +562,18 @@ class SanaPipelineES(_SanaStack):
     @torch.no_grad()
     def generate_population(self, prompt_embeds, prompt_attention_mask, theta_pop: torch.Tensor, seed: int,
                             guidance_scale: float, width_latent: int, height_latent: int,
-                            prompt_index: Optional[torch.Tensor] = None) -> torch.Tensor:
+                            prompt_index: Optional[torch.Tensor] = None,
+                            flat_seeds: Optional[Sequence[int]] = None) -> torch.Tensor:
         """SanaOneStep.generate_population's contract: all members of theta_pop [n, D] at once, VAE images
-        [n*b, 3, H, W] (member-major); every step's forward uses prompt_index."""
+        [n*b, 3, H, W] (member-major); every step's forward uses prompt_index.  flat_seeds: [b] per-image seeds,
+        image i draws its latents and step noises from its own Generator(flat_seeds[i]) (_draws' image_seeds)."""
         n = theta_pop.shape[0]
         self.ctx.theta_pop, self.ctx.n_members = theta_pop, n
         set_population(self.transformer, self.ctx)
         try:
             b = prompt_embeds.shape[0] if prompt_index is None else prompt_index.numel()
-            imgs, _ = self._sample(self._draws(b, seed, height_latent, width_latent), prompt_embeds,
+            seeds = None if flat_seeds is None else [int(s) for s in flat_seeds]
+            imgs, _ = self._sample(self._draws(b, seed, height_latent, width_latent, seeds), prompt_embeds,
                                    prompt_attention_mask, guidance_scale, reps=n, prompt_index=prompt_index)
         finally:
             set_population(self.transformer, None)

@@ -184,12 +184,19 @@ def clip_pixels(images: torch.Tensor, pil_mode: int = 0, size: int = 224, mean: 
     short edge, center crop, CLIP normalisation — bitwise equal to
     clip_preprocess(postprocess_uint8(images)) / clip_preprocess(quantize_uint8_var(images))."""
     from . import _lib
-    from .kernels import _stream
     if images.device.type != "cuda" or images.dtype != torch.bfloat16:
         raise _lib.EggrollError("clip_pixels: expected a bf16 ROCm tensor (no CPU fallback)")
     n, c, h, w = images.shape
     if c != 3:
         raise ValueError(f"clip_pixels: expected 3 channels, got {c}")
+    return _clip_pixels_call("eggroll_clip_preprocess", images, n, h, w, images.stride(), (int(pil_mode),), size, mean, std)
+
+
+def _clip_pixels_call(entry: str, images: torch.Tensor, n: int, h: int, w: int, strides, mode_arg: tuple, size: int,
+                      mean, std) -> torch.Tensor:
+    """The tap tables, scratch and launch shared by clip_pixels and clip_pixels_u8; strides = (sn, sc, sh, sw)."""
+    from . import _lib
+    from .kernels import _stream
     nh, nw = (size, int(size * w / h)) if h <= w else (int(size * h / w), size)
     tw, ktw = pil_tap_table(w, nw, images.device)
     th, kth = pil_tap_table(h, nh, images.device)
@@ -197,11 +204,25 @@ def clip_pixels(images: torch.Tensor, pil_mode: int = 0, size: int = 224, mean: 
     tmp = torch.empty((max(n * 3 * h * size, 1),), dtype=torch.uint8, device=images.device)
     mean = (ctypes.c_float * 3)(*mean)
     std = (ctypes.c_float * 3)(*std)
-    sn, sc, sh, sw = images.stride()
-    _lib.call("eggroll_clip_preprocess", images.data_ptr(), n, h, w, sn, sc, sh, sw, int(pil_mode), tw.data_ptr(),
+    sn, sc, sh, sw = strides
+    _lib.call(entry, images.data_ptr(), n, h, w, sn, sc, sh, sw, *mode_arg, tw.data_ptr(),
               th.data_ptr(), ktw, kth, nw, nh, size, ctypes.cast(mean, ctypes.c_void_p),
               ctypes.cast(std, ctypes.c_void_p), tmp.data_ptr(), out.data_ptr(), _stream(images.device))
     return out
+
+
+def clip_pixels_u8(u8: torch.Tensor, size: int = 224, mean: Sequence[float] = CLIP_MEAN,
+                   std: Sequence[float] = CLIP_STD) -> torch.Tensor:
+    """8-bit images on the device -> CLIP pixel values [n,3,size,size] fp32 (eggroll_clip_preprocess_u8): what
+    clip_pixels computes after its uint8 conversion.  u8: uint8 [n,H,W,3] of any strides: the bytes of PIL "RGB"
+    images, or a planar [n,3,H,W] tensor seen through .permute(0, 2, 3, 1)."""
+    from . import _lib
+    if not isinstance(u8, torch.Tensor) or u8.device.type != "cuda" or u8.dtype != torch.uint8:
+        raise _lib.EggrollError("clip_pixels_u8: expected a uint8 ROCm tensor (no CPU fallback)")
+    if u8.ndim != 4 or u8.shape[3] != 3:
+        raise ValueError(f"clip_pixels_u8: expected [n,H,W,3], got {tuple(u8.shape)}")
+    (n, h, w, _), (sn, sh, sw, sc) = u8.shape, u8.stride()
+    return _clip_pixels_call("eggroll_clip_preprocess_u8", u8, n, h, w, (sn, sc, sh, sw), (), size, mean, std)
 
 
 class ClipTokenizer:
@@ -444,16 +465,31 @@ class RewardModels:
         rows; pil_mode: the backend's image -> PIL conversion (0 Sana: PixArt postprocess, rounding;
         1 VAR: models/VAR.py:245-259, fp16 + truncation).  Returns per-image fp32 tensors with the
         compute_all_rewards keys."""
-        n = images.shape[0]
+        return self._score_pixels(images.shape[0], lambda s, spec: clip_pixels(
+            images[s:s + self.image_batch].to(torch.bfloat16), pil_mode, spec.size, spec.mean, spec.std),
+            prompt_index, feats)
+
+    @torch.no_grad()
+    def score_u8(self, u8_images: torch.Tensor, prompt_index: torch.Tensor,
+                 feats: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
+        """score() of images that are 8-bit already: u8_images uint8 [n,H,W,3] on the device, the bytes of the PIL
+        images themselves (a decoded PNG, kernels.images_to_u8), so there is no pil_mode.  From the pixel values
+        onward it is score()'s computation: score_u8(images_to_u8(x, mode)) == score(x, pil_mode=mode) bitwise."""
+        return self._score_pixels(u8_images.shape[0], lambda s, spec: clip_pixels_u8(
+            u8_images[s:s + self.image_batch], spec.size, spec.mean, spec.std), prompt_index, feats)
+
+    def _score_pixels(self, n: int, pixels: Callable, prompt_index: torch.Tensor,
+                      feats: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
+        """The towers and the reward arithmetic of score / score_u8; pixels(start, PixelSpec) -> the CLIP pixel
+        values of images start .. start + image_batch."""
         t_clip, t_pick = self.towers()
         same_px = self.clip_px == self.pick_px
         e_clip, e_pick = [], []
         for s in range(0, n, self.image_batch):
-            im = images[s:s + self.image_batch].to(torch.bfloat16)
-            px = clip_pixels(im, pil_mode, self.clip_px.size, self.clip_px.mean, self.clip_px.std)
+            px = pixels(s, self.clip_px)
             e_clip.append(t_clip(px))
             if not same_px:
-                px = clip_pixels(im, pil_mode, self.pick_px.size, self.pick_px.mean, self.pick_px.std)
+                px = pixels(s, self.pick_px)
             e_pick.append(t_pick(px))
         ic = torch.cat(e_clip)
         ic = ic / ic.norm(dim=-1, keepdim=True).clamp_min(1e-6)  # rewards.py:99

@@ -459,6 +459,21 @@ int eggroll_clip_preprocess(const void* img, int64_t n, int64_t H, int64_t W, in
                             int32_t kth, int64_t RW, int64_t RH, int64_t out_size, const float* mean,
                             const float* stdv, void* tmp, void* out, void* stream);
 
+/* The same two passes on images that are 8-bit already (a decoded PNG, or eggroll_images_to_u8's output): img is
+ * uint8, element (i, c, y, x) at img[i*sn + c*sc + y*sh + x*sw] (byte strides: PIL's HWC is sc = 1, sw = 3, sh = 3 W;
+ * planar CHW works too); there is no conversion step, every other argument as eggroll_clip_preprocess.   */
+int eggroll_clip_preprocess_u8(const void* img, int64_t n, int64_t H, int64_t W, int64_t sn, int64_t sc, int64_t sh,
+                               int64_t sw, const int32_t* tab_w, const int32_t* tab_h, int32_t ktw, int32_t kth,
+                               int64_t RW, int64_t RH, int64_t out_size, const float* mean, const float* stdv,
+                               void* tmp, void* out, void* stream);
+
+/* Decoder images -> the bytes of PIL "RGB" images: out uint8 [n][H][W][3] (contiguous, n*H*W*3 bytes),
+ *   out[i][y][x][c] = u8(img[i*sn + c*sc + y*sh + x*sw]),  u8 = eggroll_clip_preprocess's conversion of `mode`.
+ * img: bf16, 3 channels, any strides (in elements).  Rows of contiguous pixels (sw = 1) with W % 16 == 0 and img,
+ * out, sn, sc, sh all 16-byte aligned move 16 bytes per lane and access; everything else goes pixel by pixel. */
+int eggroll_images_to_u8(const void* img, int64_t n, int64_t H, int64_t W, int64_t sn, int64_t sc, int64_t sh,
+                         int64_t sw, int32_t mode, void* out, void* stream);
+
 /* Softmax cross-attention over a short key sequence (Sana attn2: diffusers SanaAttnProcessor2_0,
  * F.scaled_dot_product_attention with the caption mask as an additive bias):
  *   o[b,n,h,:] = softmax_j(scale * q[b,n,h,:] . k[u,j,h,:] + bias[u,j]) @ v[u,:,h,:],  u = enc_index[b]
