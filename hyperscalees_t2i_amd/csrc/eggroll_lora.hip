@@ -620,8 +620,11 @@ __device__ __forceinline__ void epi_prefetch(char* ep, int wave, int lane, int m
         }
     }
     if (bias && wave < E::BIAS_WAVES) {
+        // the range check is per 4-byte access: with an odd column count the dword holding the last bias
+        // would be cut by a 2-byte-granular limit and read as 0, so the limit covers that whole dword (its
+        // upper half, bias[N], belongs to no stored column)
         const __amdgpu_buffer_rsrc_t rz = __builtin_amdgcn_make_buffer_rsrc((void*)(bias + n0), (short)0,
-                                                                            (N - n0) * 2, 0x00020000);
+                                                                            ((N - n0) * 2 + 3) & ~3, 0x00020000);
         __builtin_amdgcn_raw_ptr_buffer_load_lds(rz, (lds_void*)(ep + E::BIAS + wave * 256), 4, vo, wave * 256, 0, 0);
     }
 }
@@ -1468,31 +1471,49 @@ int eggroll_lora_delta_f32(const float* x, int64_t ldx, const float* A, int64_t 
 // stream).  0 = automatic: the 8-phase 256x256 kernel when the grid still fills the chip, else the
 // 128x128 one-barrier tile.  8 / 9 = 8-phase with MFMA / VALU LoRA epilogue, 12 = as 8 with the
 // projection fused (linear_pop only), 128 / 256 = one-barrier tiles.
-static int lora_gemm_impl(const void* X, int64_t ldx, const void* W, int64_t ldw, const void* bias, const float* T,
-                          const float* theta_pop, int64_t ld_theta, int64_t offB, int32_t r, float scale,
-                          int64_t rows_per_member, int64_t M, int64_t N, int64_t K, void* Y, int64_t ldy,
-                          int32_t kernel, void* stream) {
+// Every argument check of the plain GEMM entry points, reported under the caller's name, before
+// anything is launched; *tsel: the kernel that will run.
+static int plain_args_ok(const char* api, int64_t ldx, int64_t ldw, int64_t ldy, int32_t r, int64_t rows_per_member,
+                         int64_t M, int64_t N, int64_t K, int32_t kernel, int* tsel) {
     EGG_CHECK_ARG(kernel == 0 || kernel == 8 || kernel == 9 || kernel == 10 || kernel == 12 || kernel == 128 ||
                       kernel == 256,
-                  "lora_gemm: kernel must be 0 (auto), 8, 9, 10, 12, 128 or 256 (got %d)", kernel);
-    EGG_CHECK_ARG(M >= 0 && N > 0 && K > 0, "lora_gemm: bad sizes M=%lld N=%lld K=%lld", (long long)M, (long long)N,
+                  "%s: kernel must be 0 (auto), 8, 9, 10, 12, 128 or 256 (got %d)", api, kernel);
+    EGG_CHECK_ARG(M >= 0 && N > 0 && K > 0, "%s: bad sizes M=%lld N=%lld K=%lld", api, (long long)M, (long long)N,
                   (long long)K);
-    EGG_CHECK_ARG(K % 64 == 0, "lora_gemm: K=%lld must be a multiple of 64", (long long)K);
-    EGG_CHECK_ARG(r >= 0 && r <= 16, "lora_gemm: r=%d out of range", r);
-    EGG_CHECK_ARG(rows_per_member > 0, "lora_gemm: rows_per_member must be > 0");
-    const int tsel = kernel ? kernel
-                            : ((M / 256) * ((N + 255) / 256) >= 512 ? gemm8_auto(M, N, r, rows_per_member, EPI_NONE) : 128);
-    const bool p8 = tsel == 8 || tsel == 9 || tsel == 10 || tsel == 12;
-    if (const int rc = gemm_args_ok("lora_gemm", ldx, ldw, ldy, rows_per_member, M, N, K, p8)) return rc;
-    if (M == 0) return EGGROLL_OK;
-    EGG_CHECK_ARG(X && W && Y, "lora_gemm: NULL pointer");
-    EGG_CHECK_ARG(r == 0 || (T && theta_pop), "lora_gemm: T / theta_pop NULL with r > 0");
+    EGG_CHECK_ARG(K % 64 == 0, "%s: K=%lld must be a multiple of 64", api, (long long)K);
+    EGG_CHECK_ARG(r >= 0 && r <= 16, "%s: r=%d out of range", api, r);
+    EGG_CHECK_ARG(rows_per_member > 0, "%s: rows_per_member must be > 0", api);
+    *tsel = kernel ? kernel
+                   : ((M / 256) * ((N + 255) / 256) >= 512 ? gemm8_auto(M, N, r, rows_per_member, EPI_NONE) : 128);
+    const bool p8 = *tsel == 8 || *tsel == 9 || *tsel == 10 || *tsel == 12;
+    return gemm_args_ok(api, ldx, ldw, ldy, rows_per_member, M, N, K, p8);
+}
+
+// The plain GEMM on kernel tsel, arguments checked by plain_args_ok (M > 0).
+static int lora_gemm_launch(const char* api, int tsel, const void* X, int64_t ldx, const void* W, int64_t ldw,
+                            const void* bias, const float* T, const float* theta_pop, int64_t ld_theta, int64_t offB,
+                            int32_t r, float scale, int64_t rows_per_member, int64_t M, int64_t N, int64_t K, void* Y,
+                            int64_t ldy, void* stream) {
+    EGG_CHECK_ARG(X && W && Y, "%s: NULL pointer", api);
+    EGG_CHECK_ARG(r == 0 || (T && theta_pop), "%s: T / theta_pop NULL with r > 0", api);
     hipStream_t st = as_stream(stream);
     const GemmArgs g{X, ldx, W, ldw, bias, T, theta_pop, ld_theta, offB, r, scale, rows_per_member, M, N, K, Y, ldy};
     if (tsel == 10 && gemm8n_ok(r, rows_per_member))  // else: kernel 8's VALU-epilogue path, as kernel 8 does
         return launch_gemm8<G8<2, 5>>(g, true, EPI_NONE, EpiArgs{}, st);
-    if (p8) return launch_gemm8<G8<2>>(g, tsel != 9 && r <= 2 && rows_per_member >= 256, EPI_NONE, EpiArgs{}, st);
+    if (tsel == 8 || tsel == 9 || tsel == 10 || tsel == 12)
+        return launch_gemm8<G8<2>>(g, tsel != 9 && r <= 2 && rows_per_member >= 256, EPI_NONE, EpiArgs{}, st);
     return tsel == 256 ? launch_gemm<kT256>(g, st) : launch_gemm<kT128>(g, st);
+}
+
+static int lora_gemm_impl(const void* X, int64_t ldx, const void* W, int64_t ldw, const void* bias, const float* T,
+                          const float* theta_pop, int64_t ld_theta, int64_t offB, int32_t r, float scale,
+                          int64_t rows_per_member, int64_t M, int64_t N, int64_t K, void* Y, int64_t ldy,
+                          int32_t kernel, void* stream) {
+    int tsel;
+    if (const int rc = plain_args_ok("lora_gemm", ldx, ldw, ldy, r, rows_per_member, M, N, K, kernel, &tsel)) return rc;
+    if (M == 0) return EGGROLL_OK;
+    return lora_gemm_launch("lora_gemm", tsel, X, ldx, W, ldw, bias, T, theta_pop, ld_theta, offB, r, scale,
+                            rows_per_member, M, N, K, Y, ldy, stream);
 }
 
 int eggroll_lora_gemm(const void* X, int64_t ldx, const void* W, int64_t ldw, const void* bias, const float* T,
@@ -1523,27 +1544,25 @@ int eggroll_lora_linear_pop_sel(const void* X, int64_t ldx, const void* W, int64
                                 const float* theta_pop, int64_t ld_theta, int64_t offA, int64_t offB, int32_t r,
                                 float scale, int64_t rows_per_member, int64_t M, int64_t N, int64_t K, void* Y,
                                 int64_t ldy, float* T_ws, int32_t kernel, void* stream) {
-    EGG_CHECK_ARG(kernel == 0 || kernel == 8 || kernel == 9 || kernel == 10 || kernel == 12 || kernel == 128 ||
-                      kernel == 256,
-                  "lora_linear_pop: kernel must be 0 (auto), 8, 9, 10, 12, 128 or 256 (got %d)", kernel);
-    EGG_CHECK_ARG(K > 0 && K % 64 == 0, "lora_linear_pop: K=%lld must be a multiple of 64", (long long)K);
-    EGG_CHECK_ARG(r >= 0 && r <= 16, "lora_linear_pop: r=%d out of range", r);
+    // every check of the GEMM before the projection is launched: a refused call launches nothing
+    int tsel;
+    if (const int rc = plain_args_ok("lora_linear_pop", ldx, ldw, ldy, r, rows_per_member, M, N, K, kernel, &tsel))
+        return rc;
     if (M == 0) return EGGROLL_OK;
+    EGG_CHECK_ARG(X && W && Y, "lora_linear_pop: NULL pointer");
+    EGG_CHECK_ARG(r == 0 || (theta_pop && T_ws), "lora_linear_pop: theta_pop / T_ws NULL with r > 0");
     if (r > 0 && fused_ok(kernel, r, K, rows_per_member)) {  // projection fused into the 8-phase GEMM
-        EGG_CHECK_ARG(X && W && Y && theta_pop && T_ws, "lora_linear_pop: NULL pointer");
         // (launch_gemm8f checks the 32-bit offsets itself: it has a third operand, AK)
-        if (const int rc = gemm_args_ok("lora_linear_pop", ldx, ldw, ldy, rows_per_member, M, N, K, false)) return rc;
         EGG_CHECK_ARG(ld_theta % 4 == 0 && offA % 4 == 0, "lora_linear_pop: theta offsets must be 16-byte aligned");
         return launch_gemm8f(X, ldx, W, ldw, bias, theta_pop, ld_theta, offA, offB, r, scale, rows_per_member, M, N,
                              K, Y, ldy, T_ws, as_stream(stream));
     }
     if (r > 0) {
-        EGG_CHECK_ARG(theta_pop && T_ws, "lora_linear_pop: theta_pop / T_ws NULL with r > 0");
         int rc = eggroll_lora_project(X, ldx, theta_pop, ld_theta, offA, r, rows_per_member, M, K, T_ws, stream);
         if (rc) return rc;
     }
-    return lora_gemm_impl(X, ldx, W, ldw, bias, T_ws, theta_pop, ld_theta, offB, r, scale, rows_per_member, M, N, K, Y,
-                          ldy, kernel == 12 ? 8 : kernel, stream);
+    return lora_gemm_launch("lora_linear_pop", tsel == 12 ? 8 : tsel, X, ldx, W, ldw, bias, T_ws, theta_pop, ld_theta,
+                            offB, r, scale, rows_per_member, M, N, K, Y, ldy, stream);
 }
 
 // The epilogue GEMM with T = X A_k^T already computed (shared by linear_pop_epi and lora_gemm_epi).
@@ -1560,21 +1579,22 @@ static int gemm_epi_impl(const void* X, int64_t ldx, const void* W, int64_t ldw,
                         : launch_gemm8<G8<2>>(g, true, epi, ea, as_stream(stream));
 }
 
-static int epi_args_ok(const void* X, int64_t ldx, const void* W, int64_t ldw, int32_t r, int64_t rows_per_member,
-                       int64_t M, int64_t N, int64_t K, const void* Y, int64_t ldy, int32_t epi, const void* res,
-                       int64_t ldr, const void* gate, int64_t gstride, int64_t rows_per_group, int32_t kernel) {
-    EGG_CHECK_ARG(kernel == 0 || kernel == 8 || kernel == 10, "lora_linear_pop_epi: kernel must be 0, 8 or 10");
-    EGG_CHECK_ARG(epi >= EPI_SILU && epi <= EPI_GELU_ERF, "lora_linear_pop_epi: epi=%d unknown", epi);
-    EGG_CHECK_ARG(r >= 0 && r <= 2, "lora_linear_pop_epi: r=%d (epilogue ops need r <= 2)", r);
-    EGG_CHECK_ARG(r == 0 || rows_per_member >= 256, "lora_linear_pop_epi: rows_per_member must be >= 256 with r > 0");
-    EGG_CHECK_ARG(M >= 0 && N > 0 && K > 0 && K % 64 == 0, "lora_linear_pop_epi: need K %% 64 == 0");
-    if (const int rc = gemm_args_ok("lora_linear_pop_epi", ldx, ldw, ldy, rows_per_member, M, N, K, true)) return rc;
+static int epi_args_ok(const char* api, const void* X, int64_t ldx, const void* W, int64_t ldw, int32_t r,
+                       int64_t rows_per_member, int64_t M, int64_t N, int64_t K, const void* Y, int64_t ldy,
+                       int32_t epi, const void* res, int64_t ldr, const void* gate, int64_t gstride,
+                       int64_t rows_per_group, int32_t kernel) {
+    EGG_CHECK_ARG(kernel == 0 || kernel == 8 || kernel == 10, "%s: kernel must be 0, 8 or 10", api);
+    EGG_CHECK_ARG(epi >= EPI_SILU && epi <= EPI_GELU_ERF, "%s: epi=%d unknown", api, epi);
+    EGG_CHECK_ARG(r >= 0 && r <= 2, "%s: r=%d (epilogue ops need r <= 2)", api, r);
+    EGG_CHECK_ARG(r == 0 || rows_per_member >= 256, "%s: rows_per_member must be >= 256 with r > 0", api);
+    EGG_CHECK_ARG(M >= 0 && N > 0 && K > 0 && K % 64 == 0, "%s: need K %% 64 == 0", api);
+    if (const int rc = gemm_args_ok(api, ldx, ldw, ldy, rows_per_member, M, N, K, true)) return rc;
     EGG_CHECK_ARG(epi == EPI_SILU || epi == EPI_GELU || epi == EPI_GELU_ERF || (res && ldr >= N),
-                  "lora_linear_pop_epi: res NULL or ldr < N");
+                  "%s: res NULL or ldr < N", api);
     EGG_CHECK_ARG((epi != EPI_GATED && epi != EPI_GATED32) || (gate && gstride >= N && rows_per_group > 0),
-                  "lora_linear_pop_epi: bad gate");
+                  "%s: bad gate", api);
     if (M == 0) return EGGROLL_OK;
-    EGG_CHECK_ARG(X && W && (Y || epi == EPI_RES32 || epi == EPI_GATED32), "lora_linear_pop_epi: NULL pointer");
+    EGG_CHECK_ARG(X && W && (Y || epi == EPI_RES32 || epi == EPI_GATED32), "%s: NULL pointer", api);
     return EGGROLL_OK;
 }
 
@@ -1589,8 +1609,8 @@ int eggroll_lora_linear_pop_epi_sel(const void* X, int64_t ldx, const void* W, i
         return eggroll_lora_linear_pop_sel(X, ldx, W, ldw, bias, theta_pop, ld_theta, offA, offB, r, scale,
                                            rows_per_member, M, N, K, Y, ldy, T_ws, kernel, stream);
     }
-    const int rc0 = epi_args_ok(X, ldx, W, ldw, r, rows_per_member, M, N, K, Y, ldy, epi, res, ldr, gate, gstride,
-                                rows_per_group, kernel);
+    const int rc0 = epi_args_ok("lora_linear_pop_epi", X, ldx, W, ldw, r, rows_per_member, M, N, K, Y, ldy, epi, res,
+                                ldr, gate, gstride, rows_per_group, kernel);
     if (rc0 || M == 0) return rc0;
     if (r > 0) {
         EGG_CHECK_ARG(theta_pop && T_ws, "lora_linear_pop_epi: theta_pop / T_ws NULL with r > 0");
@@ -1606,8 +1626,8 @@ int eggroll_lora_gemm_epi_sel(const void* X, int64_t ldx, const void* W, int64_t
                               int64_t rows_per_member, int64_t M, int64_t N, int64_t K, void* Y, int64_t ldy,
                               int32_t epi, const void* res, int64_t ldr, const void* gate, int64_t gstride,
                               int64_t rows_per_group, int32_t kernel, void* stream) {
-    const int rc0 = epi_args_ok(X, ldx, W, ldw, r, rows_per_member, M, N, K, Y, ldy, epi, res, ldr, gate, gstride,
-                                rows_per_group, kernel);
+    const int rc0 = epi_args_ok("lora_gemm_epi", X, ldx, W, ldw, r, rows_per_member, M, N, K, Y, ldy, epi, res, ldr,
+                                gate, gstride, rows_per_group, kernel);
     if (rc0 || M == 0) return rc0;
     EGG_CHECK_ARG(r == 0 || (T && theta_pop), "lora_gemm_epi: T / theta_pop NULL with r > 0");
     return gemm_epi_impl(X, ldx, W, ldw, bias, T, theta_pop, ld_theta, offB, r, scale, rows_per_member, M, N, K, Y, ldy,

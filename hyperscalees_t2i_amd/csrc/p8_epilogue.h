@@ -46,7 +46,8 @@ __device__ __forceinline__ float epi_gelu_erf(float x) {
 
 // x * sigmoid(x) on two values: the multiplies / add as packed fp32 ops (v_pk_mul_f32 / v_pk_add_f32),
 // exp2 and rcp per value: the same operations, value by value, as x * rcp(1 + __expf(-x)) (v_mul by
-// log2(e), v_exp_f32, v_add, v_rcp_f32, v_mul), so the same bits (test_lora_linear_pop_epilogue_bitexact)
+// log2(e), v_exp_f32, v_add, v_rcp_f32, v_mul), so the same bits (test_lora_linear_pop_epilogue_bitexact;
+// test_epilogue_layouts stores the same elements through this form and through epi_apply1: equal bits)
 __device__ __forceinline__ f32x2 silu2(f32x2 v) {
     f32x2 t = v * (f32x2){-1.4426950408889634f, -1.4426950408889634f};
     t.x = __builtin_amdgcn_exp2f(t.x);

@@ -33,6 +33,16 @@ def _p(t: Optional[torch.Tensor]):
     return None if t is None else t.data_ptr()
 
 
+def _out_ld(out: torch.Tensor, what: str, M: int, N: int) -> int:
+    """Row stride (ldy) of a caller's bf16 [M, N] output; its rows may be padded (a column slice of a wider
+    buffer).  Anything the kernels would have to reinterpret raises instead."""
+    _dev(out, what, torch.bfloat16, contiguous=False)
+    if tuple(out.shape) != (M, N) or out.stride(1) != 1 or (M > 1 and out.stride(0) < N):
+        raise _lib.EggrollError(f"{what}: expected a [{M}, {N}] view with unit inner stride and row stride >= {N}, "
+                                f"got shape {tuple(out.shape)} strides {tuple(out.stride())}")
+    return max(out.stride(0), N)
+
+
 def _stream(device: torch.device):
     return torch.cuda.current_stream(device).cuda_stream
 
@@ -323,6 +333,7 @@ def lora_linear_pop(x: torch.Tensor, W: torch.Tensor, bias: Optional[torch.Tenso
         _dev(bias, "lora_linear_pop(bias)", torch.bfloat16)
     if out is None:
         out = torch.empty((M, N), dtype=torch.bfloat16, device=x.device)
+    ldy = _out_ld(out, "lora_linear_pop(out)", M, N)
     if r > 0:
         _dev(theta_pop, "lora_linear_pop(theta_pop)", torch.float32)
         n_members = -(-M // rows_per_member)
@@ -336,7 +347,7 @@ def lora_linear_pop(x: torch.Tensor, W: torch.Tensor, bias: Optional[torch.Tenso
         ld_t = 0
     _lib.call("eggroll_lora_linear_pop_sel", x.data_ptr(), x.stride(0), W.data_ptr(), W.stride(0), _p(bias),
               _p(theta_pop) if r > 0 else None, ld_t, offA, offB, r, float(scale), rows_per_member, M, N, K,
-              out.data_ptr(), out.stride(0), _p(T_ws) if r > 0 else None, int(kernel), _stream(x.device))
+              out.data_ptr(), ldy, _p(T_ws) if r > 0 else None, int(kernel), _stream(x.device))
     return out
 
 
@@ -367,10 +378,10 @@ def lora_linear_pop_epi(x: torch.Tensor, W: torch.Tensor, bias: Optional[torch.T
     if f32res:
         if res is None or (code == 5 and (gate is None or gate.dtype != torch.float32)):
             raise ValueError(f"lora_linear_pop_epi({epi}): needs an fp32 res (and an fp32 gate)")
-        if out is not None:
-            _dev(out, "lora_linear_pop_epi(out)", torch.bfloat16)
     elif out is None:
         out = res if res is not None and code in (2, 3, 7) else torch.empty((M, N), dtype=torch.bfloat16, device=x.device)
+    # out is res (in place: contiguous, any leading shape) or a [M, N] view whose rows may be padded
+    ldy = N if out is None or out is res else _out_ld(out, "lora_linear_pop_epi(out)", M, N)
     pg, gst = _row_ptr(gate, "lora_linear_pop_epi(gate)", N, allow_f32=code == 5) if gate is not None else (None, 0)
     if r > 0:
         _dev(theta_pop, "lora_linear_pop_epi(theta_pop)", torch.float32)
@@ -379,7 +390,7 @@ def lora_linear_pop_epi(x: torch.Tensor, W: torch.Tensor, bias: Optional[torch.T
             T_ws = torch.empty(need, dtype=torch.float32, device=x.device)
     _lib.call("eggroll_lora_linear_pop_epi_sel", x.data_ptr(), x.stride(0), W.data_ptr(), W.stride(0), _p(bias),
               _p(theta_pop) if r > 0 else None, theta_pop.stride(0) if r > 0 else 0, offA, offB, r, float(scale),
-              rows_per_member, M, N, Kd, _p(out), N, _p(T_ws) if r > 0 else None, code,
+              rows_per_member, M, N, Kd, _p(out), ldy, _p(T_ws) if r > 0 else None, code,
               _p(res), N if res is not None else 0, pg, gst or N, int(rows_per_group), int(kernel), _stream(x.device))
     return res if f32res else out
 
@@ -405,17 +416,17 @@ def lora_gemm_epi(x: torch.Tensor, W: torch.Tensor, bias: Optional[torch.Tensor]
     if f32res:
         if res is None or (code == 5 and (gate is None or gate.dtype != torch.float32)):
             raise ValueError(f"lora_gemm_epi({epi}): needs an fp32 res (and an fp32 gate)")
-        if out is not None:
-            _dev(out, "lora_gemm_epi(out)", torch.bfloat16)
     elif out is None:
         out = res if res is not None and code in (2, 3, 7) else torch.empty((M, N), dtype=torch.bfloat16, device=x.device)
+    # out is res (in place: contiguous, any leading shape) or a [M, N] view whose rows may be padded
+    ldy = N if out is None or out is res else _out_ld(out, "lora_gemm_epi(out)", M, N)
     pg, gst = _row_ptr(gate, "lora_gemm_epi(gate)", N, allow_f32=code == 5) if gate is not None else (None, 0)
     if r > 0:
         _dev(theta_pop, "lora_gemm_epi(theta_pop)", torch.float32)
         _dev(T, "lora_gemm_epi(T)", torch.float32)
     _lib.call("eggroll_lora_gemm_epi_sel", x.data_ptr(), x.stride(0), W.data_ptr(), W.stride(0), _p(bias),
               _p(T) if r > 0 else None, _p(theta_pop) if r > 0 else None, theta_pop.stride(0) if r > 0 else 0, offB, r,
-              float(scale), rows_per_member, M, N, Kd, _p(out), N, code, _p(res), N if res is not None else 0, pg,
+              float(scale), rows_per_member, M, N, Kd, _p(out), ldy, code, _p(res), N if res is not None else 0, pg,
               gst or N, int(rows_per_group), int(kernel), _stream(x.device))
     return res if f32res else out
 
@@ -443,10 +454,11 @@ def lora_gemm(x: torch.Tensor, W: torch.Tensor, bias: Optional[torch.Tensor], T:
     N = W.shape[0]
     if out is None:
         out = torch.empty((M, N), dtype=torch.bfloat16, device=x.device)
+    ldy = _out_ld(out, "lora_gemm(out)", M, N)
     ld_t = theta_pop.stride(0) if (r > 0 and theta_pop is not None) else 0
     _lib.call("eggroll_lora_gemm_sel", x.data_ptr(), x.stride(0), W.data_ptr(), W.stride(0), _p(bias),
               _p(T) if r > 0 else None, _p(theta_pop) if r > 0 else None, ld_t, offB, r, float(scale),
-              rows_per_member, M, N, K, out.data_ptr(), out.stride(0), int(kernel), _stream(x.device))
+              rows_per_member, M, N, K, out.data_ptr(), ldy, int(kernel), _stream(x.device))
     return out
 
 

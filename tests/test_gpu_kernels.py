@@ -14,6 +14,7 @@ import torch.nn.functional as F
 from hyperscalees_t2i_amd import _lib, kernels as K
 from hyperscalees_t2i_amd.es import EggRollNoiser, paper_prompt_normalized_scores, standardize_fitness
 from oracle import eggroll_oracle as O
+from tests.lora_cases import lora_case as _lora_case, lora_ref as _lora_ref, lora_tol as _lora_tol
 
 pytestmark = pytest.mark.gpu
 
@@ -274,25 +275,6 @@ def _bf(x):
     return x.to(torch.bfloat16)
 
 
-def _lora_case(dev, M, N, Kd, r, rpm, bias=True, seed=0):
-    g = torch.Generator().manual_seed(seed)
-    x = _bf(torch.randn(M, Kd, generator=g)).to(dev)
-    W = _bf(torch.randn(N, Kd, generator=g) * 0.05).to(dev)
-    b = _bf(torch.randn(N, generator=g)).to(dev) if bias else None
-    nm = -(-M // rpm)
-    D = r * Kd + N * r + 5
-    ld = -(-D // 4) * 4
-    tp = (torch.randn(nm, ld, generator=g) * 0.1).to(dev)
-    offA, offB = 4, 4 + r * Kd
-    return x, W, b, tp, offA, offB
-
-
-def _lora_ref(x, W, b, tp, offA, offB, r, scale, rpm):
-    return O.ref_lora_linear_pop(x.float().cpu().numpy(), W.float().cpu().numpy(),
-                                 None if b is None else b.float().cpu().numpy(), tp.cpu().numpy(), offA, offB, r,
-                                 scale, rpm)
-
-
 @pytest.fixture(params=[128, 256, 8, 9, 10, 12],
                 ids=["tile128", "tile256", "tile8phase_mfma", "tile8phase_valu", "tile8phase_320", "tile8phase_fused_proj"])
 def gemm_tile(request):
@@ -316,9 +298,7 @@ def test_lora_linear_pop_vs_fp64(dev, gemm_tile, M, N, Kd, r, rpm):
     torch.cuda.synchronize()
     ref = _lora_ref(x, W, b, tp, offA, offB, r, scale, rpm)
     got = y.float().cpu().numpy()
-    # bf16 output rounding (2^-9 relative) + fp32 accumulation over K
-    tol = 2 ** -8 * np.abs(ref) + 2e-4 * math.sqrt(Kd) * np.abs(ref).std()
-    assert (np.abs(got - ref) <= tol + 1e-3).all(), float(np.abs(got - ref).max())
+    assert (np.abs(got - ref) <= _lora_tol(ref, Kd)).all(), float(np.abs(got - ref).max())
 
 
 def test_lora_linear_no_lora_matches_torch_matmul(dev, gemm_tile):
