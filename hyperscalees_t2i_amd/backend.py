@@ -348,6 +348,7 @@ class VarConfig:
     lora_seed: int = 1234
     lora_b_std: float = 0.02
     vae_chunk: int = 16
+    native_attention: bool = True           # eggroll_qk_l2norm_kv + eggroll_flash_attention (False: F.normalize + SDPA)
 
 
 class VarBackend(ESBackend):
@@ -363,7 +364,8 @@ class VarBackend(ESBackend):
     def init_and_attach_lora(self):
         c = self.cfg
         self.es_model = VARClassGenerator(model_depth=c.model_depth, device=self.device, arch=c.arch,
-                                          weight_seed=c.weight_seed, vae_chunk=c.vae_chunk)
+                                          weight_seed=c.weight_seed, vae_chunk=c.vae_chunk,
+                                          native_attention=c.native_attention)
         d = Path(c.ckpt_dir)
         vae_ckpt, var_ckpt = d / "vae_ch160v4096z32.pth", d / f"var_d{self.es_model.model_depth}.pth"
         if vae_ckpt.is_file() and var_ckpt.is_file():

@@ -2,7 +2,8 @@
 //
 //   k_cross_attn, k_cross_attn_h2 : a short key sequence staged whole in LDS (Sana attn2, the CLIP towers,
 //                  Infinity's text cross-attention); two-pass, or online softmax over two key halves
-//   k_flash_attn : head dim 128, any key count, no mask (Z-Image self-attention, Infinity over its KV cache)
+//   k_flash_attn : head dim 128 or 64, any key count, no mask (Z-Image self-attention; Infinity and VAR over
+//                  their KV caches)
 //   k_seq_attn   : the prompt encoders' self-attention (T5 relative bias, Gemma-2 soft-cap, Qwen3 causal)
 #include "frag.h"
 
@@ -400,12 +401,14 @@ __global__ __launch_bounds__(64 * NWAVE) void k_cross_attn_h2(const unsigned sho
 }
 
 // ------------------------------------------------------------------------------------
-// Flash attention, head dim 128 (Z-Image self-attention; Infinity's cosine attention over the KV cache):
+// Flash attention, head dim HD = 128 (Z-Image self-attention; Infinity's cosine attention over the KV cache)
+// or 64 (VAR's L2-normalised attention over its KV cache):
 //   o[b, n, h, :] = softmax_j(scale * q[b,n,h,:] . k[b,j,h,:]) @ v[b, :, h, :],  j < Lk, no mask.
-// q / k / v / o: [B][rows][heads * 128] bf16 views with their own batch and row strides (a KV cache
-// [B][ltot][C] is read in place).  Workgroup = (b, h, 128-query block), 4 waves x 32 queries; keys in
-// blocks of 64 staged in LDS (k and v [64][136] bf16), the next block held in registers while this one
-// computes.  Per key block and wave, MFMA 16x16x32 bf16, fp32 accumulation, the k_cross_attn layout:
+// q / k / v / o: [B][rows][heads * HD] bf16 views with their own batch and row strides (a KV cache
+// [B][ltot][C] is read in place).  Workgroup = (b, h, 64 QF-query block), 4 waves x 16 QF queries; keys in
+// blocks of 64 staged in LDS (k and v [64][RS] bf16), the next block held in registers while this one
+// computes.  Key rows >= Lk are never read (the last key's row is read in their place and zeroed), so a cache
+// slice of uninitialised memory behind Lk is harmless.  Per key block and wave, MFMA 16x16x32 bf16, fp32 accumulation, the k_cross_attn layout:
 //   S^T = K Q^T   (Q^T fragments stay in registers for the whole key sweep; each lane: 4 keys of ONE query)
 //   online softmax in base 2: m' = max(m, rowmax), O *= 2^(m - m'), P = 2^(S - m'), per-lane partial row
 //                 sums rescaled the same way and reduced over the 4 lane groups once at the end
@@ -415,25 +418,29 @@ __global__ __launch_bounds__(64 * NWAVE) void k_cross_attn_h2(const unsigned sho
 // (ds_read_b128, lane groups {0-3,12-15,20-27}...: 8 rows x 2 chunks) and the V^T reads (ds_read_b64_tr_b16,
 // 32-lane groups: 8 rows x 32 B) both cover 64 distinct banks; the first form's 136 (4 banks apart) left
 // 38 % of the LDS cycles to bank conflicts (PMC SQ_LDS_BANK_CONFLICT / SQ_LDS_IDX_ACTIVE)
-constexpr int FA_HD = 128, FA_KB = 64, FA_RS = FA_HD + 16;
+// Head dim 64: row stride 72 bf16 = 36 dwords (k_seq_attn<SA_RELBIAS>'s, measured there), rows 4 banks apart:
+// the 4 chunks x 16 rows of a k read and the 8 rows x 32 B of a V^T read each cover 64 distinct banks.  k + v of
+// a block are 18 KB and the qf 2 instance holds 32 accumulator registers, so 4 / 3 / 2 workgroups per CU at
+// qf 1 / 2 / 4 (128 / 168 / 256 VGPRs) against 3 / 2 / 1 at head dim 128.
+constexpr int FA_HD = 128, FA_KB = 64, FA_RS = FA_HD + 16, FA_RS64 = 64 + 8;
 typedef float fa_f32x2 __attribute__((ext_vector_type(2)));
 
-template <int QF>
-__global__ __launch_bounds__(256, QF == 1 ? 3 : (QF == 2 ? 2 : 1)) void k_flash_attn(const unsigned short* __restrict__ q, int64_t q_bs, int64_t ldq,
+template <int HD, int RS, int QF, int MINB>
+__global__ __launch_bounds__(256, MINB) void k_flash_attn(const unsigned short* __restrict__ q, int64_t q_bs, int64_t ldq,
                                                     const unsigned short* __restrict__ k, int64_t k_bs, int64_t ldk,
                                                     const unsigned short* __restrict__ v, int64_t v_bs, int64_t ldv,
                                                     int heads, int Nq, int Lk, int nqb, float scale_log2,
                                                     unsigned short* __restrict__ o, int64_t o_bs, int64_t ldo) {
-    constexpr int QW = 16 * QF, KSN = FA_HD / 32, DF = FA_HD / 16, KF = FA_KB / 16, CH = FA_HD / 8;
-    constexpr int UNITS = 2 * FA_KB * CH / 256;   // 16-B chunks of k + v per thread per key block (8)
-    __shared__ __attribute__((aligned(16))) unsigned short sk[FA_KB * FA_RS];
-    __shared__ __attribute__((aligned(16))) unsigned short sv[FA_KB * FA_RS];
+    constexpr int QW = 16 * QF, KSN = HD / 32, DF = HD / 16, KF = FA_KB / 16, CH = HD / 8;
+    constexpr int UNITS = 2 * FA_KB * CH / 256;   // 16-B chunks of k + v per thread per key block (8 at head dim 128, 4 at 64)
+    __shared__ __attribute__((aligned(16))) unsigned short sk[FA_KB * RS];
+    __shared__ __attribute__((aligned(16))) unsigned short sv[FA_KB * RS];
     const int bid = xcd_remap(blockIdx.x, gridDim.x);
     const int qb = bid % nqb, bh = bid / nqb;
     const int b = bh / heads, h = bh - b * heads;
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, r16 = lane & 15, g = lane >> 4;
-    const unsigned short* kb_ = k + (int64_t)b * k_bs + (int64_t)h * FA_HD;
-    const unsigned short* vb_ = v + (int64_t)b * v_bs + (int64_t)h * FA_HD;
+    const unsigned short* kb_ = k + (int64_t)b * k_bs + (int64_t)h * HD;
+    const unsigned short* vb_ = v + (int64_t)b * v_bs + (int64_t)h * HD;
     // Q^T fragments (B operand): dims 32 ks + 8 g .. +7 of query 16 x + r16 of this wave's 32
     la_bf16x8 bq[QF][KSN];
     const int q0 = qb * (4 * QW) + w * QW;
@@ -444,7 +451,7 @@ __global__ __launch_bounds__(256, QF == 1 ? 3 : (QF == 2 ? 2 : 1)) void k_flash_
         for (int ks = 0; ks < KSN; ++ks) {
             u16x8m t = u16x8m{0, 0, 0, 0, 0, 0, 0, 0};
             if (qr < Nq)
-                t = *reinterpret_cast<const u16x8m*>(q + (int64_t)b * q_bs + (int64_t)qr * ldq + (int64_t)h * FA_HD +
+                t = *reinterpret_cast<const u16x8m*>(q + (int64_t)b * q_bs + (int64_t)qr * ldq + (int64_t)h * HD +
                                                      32 * ks + 8 * g);
             bq[x][ks] = __builtin_bit_cast(la_bf16x8, t);
         }
@@ -469,7 +476,7 @@ __global__ __launch_bounds__(256, QF == 1 ? 3 : (QF == 2 ? 2 : 1)) void k_flash_
             const int c = tid + 256 * i;
             const int kv = c / (FA_KB * CH), rc = c - kv * (FA_KB * CH);
             const int r = rc / CH, cc = rc - r * CH;
-            *reinterpret_cast<u16x8m*>((kv ? sv : sk) + r * FA_RS + cc * 8) = pre[i];
+            *reinterpret_cast<u16x8m*>((kv ? sv : sk) + r * RS + cc * 8) = pre[i];
         }
     };
     la_f32x4 oc[QF][DF];
@@ -495,7 +502,7 @@ __global__ __launch_bounds__(256, QF == 1 ? 3 : (QF == 2 ? 2 : 1)) void k_flash_
         for (int ks = 0; ks < KSN; ++ks) {
 #pragma unroll
             for (int f = 0; f < KF; ++f) {
-                const la_bf16x8 a = *reinterpret_cast<const la_bf16x8*>(sk + (16 * f + r16) * FA_RS + 32 * ks + 8 * g);
+                const la_bf16x8 a = *reinterpret_cast<const la_bf16x8*>(sk + (16 * f + r16) * RS + 32 * ks + 8 * g);
                 // the first k-step takes a literal zero accumulator (no per-block zeroing of 32 registers)
 #pragma unroll
                 for (int x = 0; x < QF; ++x)
@@ -561,7 +568,7 @@ __global__ __launch_bounds__(256, QF == 1 ? 3 : (QF == 2 ? 2 : 1)) void k_flash_
                 }
 #pragma unroll
             for (int d = 0; d < DF; ++d) {
-                const la_bf16x8 av = xa_tr8_perm<FA_RS>(sv + (32 * j) * FA_RS + 16 * d, lane);
+                const la_bf16x8 av = xa_tr8_perm<RS>(sv + (32 * j) * RS + 16 * d, lane);
 #pragma unroll
                 for (int x = 0; x < QF; ++x) oc[x][d] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av, bp[x], oc[x][d], 0, 0, 0);
             }
@@ -574,7 +581,7 @@ __global__ __launch_bounds__(256, QF == 1 ? 3 : (QF == 2 ? 2 : 1)) void k_flash_
         const int qr = q0 + 16 * x + r16;
         if (qr < Nq) {
             const float inv = 1.0f / sum;
-            unsigned short* dst = o + (int64_t)b * o_bs + (int64_t)qr * ldo + (int64_t)h * FA_HD + 4 * g;
+            unsigned short* dst = o + (int64_t)b * o_bs + (int64_t)qr * ldo + (int64_t)h * HD + 4 * g;
 #pragma unroll
             for (int d = 0; d < DF; ++d) {
                 u16x4m t;
@@ -936,20 +943,26 @@ extern "C" int eggroll_flash_attention_sel(const void* q, int64_t q_bs, int64_t 
                                            int64_t heads, int64_t Nq, int64_t Lk, int64_t head_dim, float scale, void* o,
                                            int64_t o_bs, int64_t ldo, int32_t qf, void* stream) {
     EGG_CHECK_ARG(qf == 0 || qf == 1 || qf == 2 || qf == 4, "flash_attention: qf must be 0 (auto), 1, 2 or 4");
-    if (qf == 0) qf = 2;
-    EGG_CHECK_ARG(head_dim == FA_HD, "flash_attention: head_dim %lld unsupported (128)", (long long)head_dim);
+    EGG_CHECK_ARG(head_dim == 64 || head_dim == FA_HD, "flash_attention: head_dim %lld unsupported (64, 128)",
+                  (long long)head_dim);
     EGG_CHECK_ARG(B >= 0 && heads > 0 && Nq >= 0 && Lk >= 1, "flash_attention: bad sizes");
+    // automatic: 32 queries per wave; at head dim 64 (VAR: 1 ... 256 queries a scale) 16 where 64-query workgroups
+    // pad the queries with fewer dead rows than 128-query ones (measured at B 128, 16 heads: 8.1 vs 11.2 us at
+    // Nq <= 9, 25 vs 31 at 64, 109 vs 117 at 169; 48 vs 45 at 100 and 228 vs 193 at 256, where they pad alike)
+    if (qf == 0) qf = head_dim == 64 && (Nq + 63) / 64 * 64 < (Nq + 127) / 128 * 128 ? 1 : 2;
     const int64_t qwg = 4 * 16 * qf, nqb = (Nq + qwg - 1) / qwg;
     // a sequence too long for the kernel's int counts is reported as such, after the pointer checks, not as a grid
     const bool fits = Nq < (1ll << 31) && Lk < (1ll << 31);
     bool go;
-    if (int rc = attn_args("flash_attention", FA_HD, heads, heads, q, ldq, k, ldk, v, ldv, o, ldo,
+    if (int rc = attn_args("flash_attention", head_dim, heads, heads, q, ldq, k, ldk, v, ldv, o, ldo,
                            q_bs % 8 == 0 && k_bs % 8 == 0 && v_bs % 8 == 0 && o_bs % 4 == 0, B == 0 || Nq == 0, nullptr,
                            false, fits ? B * heads * nqb : 0, &go))
         return rc;
     if (!go) return EGGROLL_OK;
     EGG_CHECK_ARG(fits, "flash_attention: sequence too long");
-    auto* kern = qf == 4 ? k_flash_attn<4> : (qf == 1 ? k_flash_attn<1> : k_flash_attn<2>);
+    auto* kern = head_dim == 64
+        ? (qf == 4 ? k_flash_attn<64, FA_RS64, 4, 2> : (qf == 1 ? k_flash_attn<64, FA_RS64, 1, 4> : k_flash_attn<64, FA_RS64, 2, 3>))
+        : (qf == 4 ? k_flash_attn<FA_HD, FA_RS, 4, 1> : (qf == 1 ? k_flash_attn<FA_HD, FA_RS, 1, 3> : k_flash_attn<FA_HD, FA_RS, 2, 2>));
     hipLaunchKernelGGL(kern, dim3((unsigned)(B * heads * nqb)), dim3(256), 0, as_stream(stream),
                        (const unsigned short*)q, q_bs, ldq, (const unsigned short*)k, k_bs, ldk,
                        (const unsigned short*)v, v_bs, ldv, (int)heads, (int)Nq, (int)Lk, (int)nqb,

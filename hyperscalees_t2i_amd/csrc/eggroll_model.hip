@@ -1618,6 +1618,97 @@ extern "C" int eggroll_qk_norm_rope_kv(void* x, int64_t ldx, int64_t rows, int32
     return EGGROLL_OK;
 }
 
+// ------------------------------------------------------------------------------------
+// q / k L2 normalisation, per-head q scale and KV-cache append at head dim 64 (VAR's attn_l2_norm attention,
+// basic_var.py:96-110), on the rows of one fused qkv GEMM output, one launch:
+//   q: y = x / max(|x|_2, eps) * qscale[h]   in place (F.normalize(x.float(), dim=-1).mul_(scale): fp32, a true
+//                                            division, one bf16 rounding)
+//   k: y = x / max(|x|_2, eps)               to kout at (row / rps) * out_bs + (row0 + row % rps) * out_ld + 64 h
+//                                            (k_qk_norm_rope's cache addressing), or in place without kout
+//   v: copied to vout at the same position.
+// 8 lanes per (part, row, head) segment of 64 values, one 16-byte load and store per lane; the segments of the
+// parts present follow each other in the grid (`parts`: 2 bits per slot, 0 = q, 1 = k, 2 = v), so q, k and v
+// never share a 16-byte chunk or a segment and a block diverges at most at the two part boundaries.
+// ------------------------------------------------------------------------------------
+__device__ __forceinline__ float seg8_sum(float v) {
+    v += dpp_f<0x141>(v);  // row_half_mirror: lane i <-> 7 - i; every quad now holds the four pair sums
+    v += dpp_f<0x4E>(v);   // quad_perm [2,3,0,1] = xor 2
+    v += dpp_f<0xB1>(v);   // quad_perm [1,0,3,2] = xor 1
+    return v;
+}
+
+__global__ __launch_bounds__(256) void k_qk_l2norm_kv(unsigned short* __restrict__ q, int64_t ldq,
+                                                      unsigned short* __restrict__ k, int64_t ldk,
+                                                      const unsigned short* __restrict__ v, int64_t ldv, int heads,
+                                                      float eps, const float* __restrict__ qscale, int64_t segs,
+                                                      int nparts, int parts, unsigned short* __restrict__ kout,
+                                                      unsigned short* __restrict__ vout, int64_t out_bs, int64_t out_ld,
+                                                      int64_t rps, int64_t row0) {
+    const int64_t gseg = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 3;
+    const int l = threadIdx.x & 7;
+    const bool live = gseg < segs * nparts;
+    const int slot = live ? (int)(gseg / segs) : 0;
+    const int part = (parts >> (2 * slot)) & 3;
+    const int64_t seg = live ? gseg - slot * segs : 0;
+    const int64_t row = seg / heads;
+    const int col = (int)(seg - row * heads) * 64 + l * 8;
+    unsigned short* src = part == 0 ? q + row * ldq : (part == 1 ? k + row * ldk : const_cast<unsigned short*>(v) + row * ldv);
+    u16x8m x = u16x8m{0, 0, 0, 0, 0, 0, 0, 0};
+    if (live) x = *reinterpret_cast<const u16x8m*>(src + col);
+    float f[8], ss = 0.f;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        f[i] = b2f(x[i]);
+        ss += f[i] * f[i];
+    }
+    ss = seg8_sum(ss);   // within the 8-lane segment (live or dead as a whole)
+    if (!live) return;
+    const int64_t orow = (row / rps) * out_bs + (row0 + row % rps) * out_ld + col;
+    if (part == 2) {
+        *reinterpret_cast<u16x8m*>(vout + orow) = x;
+        return;
+    }
+    const float den = fmaxf(sqrtf(ss), eps);
+    const float hs = part == 0 && qscale ? qscale[col >> 6] : 1.0f;
+    u16x8m o;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) o[i] = f2b(f[i] / den * hs);
+    *reinterpret_cast<u16x8m*>(part == 1 && kout ? kout + orow : src + col) = o;
+}
+
+extern "C" int eggroll_qk_l2norm_kv(void* q, int64_t ldq, void* k, int64_t ldk, const void* v, int64_t ldv,
+                                    int64_t rows, int32_t heads, int32_t head_dim, float eps, const float* qscale,
+                                    void* kout, void* vout, int64_t out_bs, int64_t out_ld, int64_t rows_per_seq,
+                                    int64_t row0, void* stream) {
+    EGG_CHECK_ARG(head_dim == 64, "qk_l2norm_kv: head_dim must be 64 (got %d)", head_dim);
+    const int64_t C = (int64_t)heads * 64;
+    EGG_CHECK_ARG(rows >= 0 && heads > 0 && eps >= 0.0f && eps < INFINITY, "qk_l2norm_kv: bad sizes / eps");
+    EGG_CHECK_ARG((!q || (ldq >= C && ldq % 8 == 0)) && (!k || (ldk >= C && ldk % 8 == 0)) &&
+                      (!v || (ldv >= C && ldv % 8 == 0)),
+                  "qk_l2norm_kv: bad strides (a multiple of 8, >= heads * 64)");
+    EGG_CHECK_ARG((!kout || k) && (!qscale || q) && !v == !vout,
+                  "qk_l2norm_kv: kout needs k, qscale needs q, v and vout come together");
+    EGG_CHECK_ARG((!kout && !vout) || (rows_per_seq > 0 && row0 >= 0 && out_ld >= C && out_ld % 8 == 0 &&
+                                       out_bs % 8 == 0 && out_bs >= (row0 + rows_per_seq) * out_ld),
+                  "qk_l2norm_kv: bad output geometry");
+    EGG_CHECK_ARG(((uintptr_t)q & 15) == 0 && ((uintptr_t)k & 15) == 0 && ((uintptr_t)v & 15) == 0 &&
+                      ((uintptr_t)kout & 15) == 0 && ((uintptr_t)vout & 15) == 0 && ((uintptr_t)qscale & 3) == 0,
+                  "qk_l2norm_kv: q / k / v / kout / vout must be 16-byte aligned, qscale 4-byte aligned");
+    int nparts = 0, parts = 0;
+    const void* present[3] = {q, k, v};
+    for (int p = 0; p < 3; ++p)
+        if (present[p]) parts |= p << (2 * nparts++);
+    if (rows == 0 || nparts == 0) return EGGROLL_OK;
+    const int64_t segs = rows * heads;
+    EGG_CHECK_ARG(rows < (1ll << 31) && segs * nparts < (1ll << 31) / 8, "qk_l2norm_kv: too many rows");
+    hipLaunchKernelGGL(k_qk_l2norm_kv, dim3((unsigned)((segs * nparts * 8 + 255) / 256)), dim3(256), 0, as_stream(stream),
+                       (unsigned short*)q, ldq, (unsigned short*)k, ldk, (const unsigned short*)v, ldv, (int)heads, eps,
+                       qscale, segs, nparts, parts, (unsigned short*)kout, (unsigned short*)vout, out_bs, out_ld,
+                       (kout || vout) ? rows_per_seq : 1, row0);
+    EGG_CHECK_LAUNCH("qk_l2norm_kv");
+    return EGGROLL_OK;
+}
+
 extern "C" int eggroll_rownorm(const void* x, int64_t rows, int64_t C, float eps, int32_t layer, const void* w,
                                const void* b, const void* mscale, const void* mshift, int64_t mstride,
                                int64_t rows_per_group, int32_t act, const void* res, void* out, void* stream) {

@@ -759,6 +759,45 @@ def qk_norm_rope_kv(x: torch.Tensor, w: torch.Tensor, eps: float, cos: torch.Ten
                 f"rows{x.shape[0]}")
 
 
+def qk_l2norm_kv(q: Optional[torch.Tensor], k: Optional[torch.Tensor], v: Optional[torch.Tensor], heads: int,
+                 eps: float = 1e-12, qscale: Optional[torch.Tensor] = None, kout: Optional[torch.Tensor] = None,
+                 vout: Optional[torch.Tensor] = None, rows_per_seq: int = 1, row0: int = 0) -> None:
+    """eggroll_qk_l2norm_kv (head dim 64): q, k, v [rows, >= heads*64] bf16 views with unit inner stride (the
+    column slices of one fused qkv GEMM output), each optional.  q <- q / max(|q|_2, eps) * qscale[h] in place
+    (qscale fp32 [heads], optional); k normalised into kout[r // rows_per_seq, row0 + r % rows_per_seq] (kout a
+    [seq, ltot, C] bf16 cache with unit inner stride; None: in place); v copied into vout at the same positions."""
+    rows = next((t.shape[0] for t in (q, k, v) if t is not None), 0)
+    for t, nm in ((q, "q"), (k, "k"), (v, "v")):
+        if t is not None:
+            _dev(t, f"qk_l2norm_kv({nm})", torch.bfloat16, contiguous=False)
+            if t.dim() != 2 or t.stride(1) != 1 or t.shape[0] != rows or t.shape[1] < heads * 64:
+                raise ValueError(f"qk_l2norm_kv: {nm} {tuple(t.shape)} / {t.stride()} vs {rows} rows of {heads} heads")
+    if qscale is not None:
+        _dev(qscale, "qk_l2norm_kv(qscale)", torch.float32)
+        if q is None or qscale.numel() != heads:
+            raise ValueError(f"qk_l2norm_kv: qscale {tuple(qscale.shape)} needs q and {heads} heads")
+    if (kout is not None and k is None) or ((v is None) != (vout is None)):
+        raise ValueError("qk_l2norm_kv: kout needs k; v and vout come together")
+    ob = ol = 0
+    for t, nm in ((kout, "kout"), (vout, "vout")):
+        if t is None:
+            continue
+        _dev(t, f"qk_l2norm_kv({nm})", torch.bfloat16, contiguous=False)
+        if (t.dim() != 3 or t.stride(2) != 1 or t.shape[2] < heads * 64 or rows_per_seq < 1 or row0 < 0
+                or t.shape[0] * rows_per_seq != rows or row0 + rows_per_seq > t.shape[1]):
+            raise ValueError(f"qk_l2norm_kv: {nm} {tuple(t.shape)} vs {rows} rows of {rows_per_seq} at row {row0}")
+        if ob and (ob, ol) != (t.stride(0), t.stride(1)):
+            raise ValueError("qk_l2norm_kv: kout and vout must share their strides")
+        ob, ol = t.stride(0), t.stride(1)
+    first = next((t for t in (q, k, v) if t is not None), None)
+    e0 = OpTimer.begin()
+    _lib.call("eggroll_qk_l2norm_kv", _p(q), q.stride(0) if q is not None else 0, _p(k),
+              k.stride(0) if k is not None else 0, _p(v), v.stride(0) if v is not None else 0, rows, int(heads), 64,
+              float(eps), _p(qscale), _p(kout), _p(vout), ob, ol, int(rows_per_seq), int(row0),
+              _stream(first.device) if first is not None else None)
+    OpTimer.end(e0, "qk_l2norm_kv", 4.0 * rows * heads * 64 * sum(t is not None for t in (q, k, v)), f"rows{rows}")
+
+
 def gated_residual_(x: torch.Tensor, y: torch.Tensor, gate: torch.Tensor, rows_per_group: int) -> torch.Tensor:
     """x += gate[g] * y in place (g = row // rows_per_group); gate a [groups, C] view."""
     _dev(x, "gated_residual(x)", torch.bfloat16)
@@ -1180,26 +1219,29 @@ def cross_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, B: int, N
 
 def flash_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: float,
                     out: Optional[torch.Tensor] = None, qf: int = 0) -> torch.Tensor:
-    """softmax(scale * q k^T) v on MFMA (eggroll_flash_attention), head dim 128, no mask.  q [B, Nq, H, 128],
-    k / v [B, Lk, H, 128] bf16 views with unit inner stride and heads 128 apart (batch and row strides
-    free: a KV-cache slice is read in place).  Returns [B, Nq, H, 128] bf16 (or writes `out`)."""
+    """softmax(scale * q k^T) v on MFMA (eggroll_flash_attention), head dim D = 64 or 128, no mask.  q [B, Nq, H, D],
+    k / v [B, Lk, H, D] bf16 views with unit inner stride and heads D apart (batch and row strides free: a
+    KV-cache slice is read in place).  Returns [B, Nq, H, D] bf16 (or writes `out`)."""
+    D = q.shape[-1] if isinstance(q, torch.Tensor) and q.dim() == 4 else 0
     for t, nm in ((q, "q"), (k, "k"), (v, "v")):
-        if t.device.type != "cuda" or t.dtype != torch.bfloat16 or t.dim() != 4 or t.stride(3) != 1 or t.stride(2) != 128:
-            raise _lib.EggrollError(f"flash_attention({nm}): expected a bf16 device view [B, S, H, 128] with heads "
-                                    f"128 apart, got {tuple(t.shape)} / {t.stride()}")
-    B, Nq, H, D = q.shape
-    if D != 128 or k.shape[0] != B or v.shape[0] != B or k.shape[2] != H or v.shape[2] != H or k.shape[1] != v.shape[1]:
+        if t.device.type != "cuda" or t.dtype != torch.bfloat16 or t.dim() != 4 or t.stride(3) != 1 or t.stride(2) != D:
+            raise _lib.EggrollError(f"flash_attention({nm}): expected a bf16 device view [B, S, H, D] with heads "
+                                    f"D = {D} apart, got {tuple(t.shape)} / {t.stride()}")
+    B, Nq, H, _ = q.shape
+    if (k.shape[0] != B or v.shape[0] != B or k.shape[2] != H or v.shape[2] != H or k.shape[1] != v.shape[1]
+            or k.shape[3] != D or v.shape[3] != D):
         raise ValueError(f"flash_attention: q {tuple(q.shape)}, k {tuple(k.shape)}, v {tuple(v.shape)}")
     if out is None:
         out = torch.empty((B, Nq, H, D), dtype=torch.bfloat16, device=q.device)
-    elif out.dtype != torch.bfloat16 or out.stride(3) != 1 or out.stride(2) != 128 or tuple(out.shape) != (B, Nq, H, D):
-        raise ValueError("flash_attention: out must be a bf16 [B, Nq, H, 128] view with heads 128 apart")
+    elif out.dtype != torch.bfloat16 or out.stride(3) != 1 or out.stride(2) != D or tuple(out.shape) != (B, Nq, H, D):
+        raise ValueError(f"flash_attention: out must be a bf16 [B, Nq, H, {D}] view with heads {D} apart")
     e0 = OpTimer.begin()
+    # the library refuses every head dim but 64 and 128, before any launch
     _lib.call("eggroll_flash_attention_sel", q.data_ptr(), q.stride(0), q.stride(1), k.data_ptr(), k.stride(0),
-              k.stride(1), v.data_ptr(), v.stride(0), v.stride(1), B, H, Nq, k.shape[1], 128, float(scale), out.data_ptr(),
+              k.stride(1), v.data_ptr(), v.stride(0), v.stride(1), B, H, Nq, k.shape[1], D, float(scale), out.data_ptr(),
               out.stride(0), out.stride(1), int(qf), _stream(q.device))
-    OpTimer.end(e0, "flash_attention", 2.0 * B * H * 128 * (2 * Nq + 2 * k.shape[1]), f"B{B} Nq{Nq} Lk{k.shape[1]} h{H}",
-                flops=4.0 * B * H * Nq * k.shape[1] * 128)
+    OpTimer.end(e0, "flash_attention", 2.0 * B * H * D * (2 * Nq + 2 * k.shape[1]),
+                f"B{B} Nq{Nq} Lk{k.shape[1]} h{H} d{D}", flops=4.0 * B * H * Nq * k.shape[1] * D)
     return out
 
 

@@ -14,7 +14,11 @@ What is different from the reference, by design:
     PEFT target is an `eggroll_lora_linear_pop` (LoRA'd GEMM per member, rows_per_member = 2B*l);
   * the AdaLN modulations depend only on the class condition, so they are computed once per
     generation instead of once per scale (same values: var.py:165 recomputes the same function);
-  * the KV cache is preallocated [seq, heads, L, 64] per block and written in place (var: cat);
+  * the KV cache is preallocated per block and written in place (var: cat): token-major [2, seq, L, C] on the
+    native attention path (`VARPopulationInfer.use_kernel`: eggroll_qk_l2norm_kv normalises q in place and appends
+    k / v to the cache in one launch, eggroll_flash_attention at head dim 64 reads q from the qkv GEMM output and
+    the cache slice in place, and the GELU / gated residuals are GEMM epilogues where those apply), head-major
+    [2, seq, heads, L, 64] on the torch path (F.normalize + SDPA, kept as the A/B baseline);
   * transformer activations are bf16 (MFMA), the reference runs fp16 autocast on CUDA
     (models/VAR.py:298-304); the token-map / f_hat path (codebook, bicubic / area resampling, Phi)
     stays fp32 as in the reference; the VQVAE decoder runs bf16 channels-last convolutions;
@@ -97,6 +101,7 @@ class VARSelfAttention(nn.Module):
         epilogue, and the per-head q multiplier exp(min(scale_mul, log 100))."""
         self.qkv_bias = torch.cat((self.q_bias, torch.zeros_like(self.q_bias), self.v_bias)).to(torch.bfloat16)
         self.q_mul = self.scale_mul_1H11.float().clamp_max(self.max_scale_mul).exp()   # [1, H, 1, 1]
+        self.q_mul_h = self.q_mul.reshape(-1).contiguous()                             # fp32 [H]: eggroll_qk_l2norm_kv's qscale
 
     def qkv(self, h: torch.Tensor) -> torch.Tensor:
         """basic_var.py:93 calls F.linear(weight=self.mat_qkv.weight, ...) instead of the module: under
@@ -414,17 +419,38 @@ def sample_population(logits: torch.Tensor, gens: Sequence[torch.Generator], top
 class VARPopulationInfer:
     """var.py:126-190 `autoregressive_infer_cfg` for n members at once (more_smooth=False)."""
 
-    def __init__(self, var: VARTransformer, vae: VQVAEDecode):
+    def __init__(self, var: VARTransformer, vae: VQVAEDecode, use_kernel: bool = True):
         self.var, self.vae = var, vae
+        # eggroll_qk_l2norm_kv + eggroll_flash_attention at head dim 64, GELU / gated residuals as GEMM epilogues
+        # (False: the torch forms, F.normalize + SDPA over a head-major cache: A/B, tests)
+        self.use_kernel = use_kernel
         self._kv: Dict[Tuple, List[torch.Tensor]] = {}
 
     def _caches(self, N2: int, dev) -> List[torch.Tensor]:
         a = self.var.arch
-        key = (N2, str(dev))
+        key = (N2, str(dev), bool(self.use_kernel))
         if key not in self._kv:
-            self._kv = {key: [torch.empty((2, N2, a.heads, a.L, 64), dtype=torch.bfloat16, device=dev)
-                              for _ in range(a.depth)]}
+            shape = (2, N2, a.L, a.C) if self.use_kernel else (2, N2, a.heads, a.L, 64)
+            self._kv = {key: [torch.empty(shape, dtype=torch.bfloat16, device=dev) for _ in range(a.depth)]}
         return self._kv[key]
+
+    def _block_native(self, blk: VARBlock, x, ada, kv, l: int, cur: int):
+        """One block on the native path, in place on x [N2*l, C]; kv [2, N2, L, C]."""
+        a = self.var.arch
+        C, H = a.C, a.heads
+        N2 = x.shape[0] // l
+        at = blk.attn
+        h = K.rownorm(x, a.norm_eps, layer=True, mscale=ada[:, 2 * C:3 * C], mshift=ada[:, 4 * C:5 * C], rows_per_group=l)
+        qkv = at.qkv(h)                                                                # [N2*l, 3C]
+        # q: L2 norm and the per-head scale in place; k: L2 norm written straight into the cache slice, v alongside
+        K.qk_l2norm_kv(qkv[:, :C], qkv[:, C:2 * C], qkv[:, 2 * C:], H, 1e-12, qscale=at.q_mul_h, kout=kv[0],
+                       vout=kv[1], rows_per_seq=l, row0=cur)
+        o = K.flash_attention(qkv.view(N2, l, 3, H, 64)[:, :, 0], kv[0, :, :cur + l].view(N2, cur + l, H, 64),
+                              kv[1, :, :cur + l].view(N2, cur + l, H, 64), 1.0).view(N2 * l, C)
+        at.proj(o, epi="gated", res=x, gate=ada[:, 0:C], rows_per_group=l)
+        h = K.rownorm(x, a.norm_eps, layer=True, mscale=ada[:, 3 * C:4 * C], mshift=ada[:, 5 * C:6 * C], rows_per_group=l)
+        f = blk.ffn.fc1(h, epi="gelu")          # GELU(tanh) in the GEMM epilogue where it applies
+        blk.ffn.fc2(f, epi="gated", res=x, gate=ada[:, C:2 * C], rows_per_group=l)
 
     @torch.no_grad()
     def run(self, label_B: torch.Tensor, n: int, g_seed: int, cfg: float, top_k: int, top_p: float,
@@ -455,6 +481,9 @@ class VARPopulationInfer:
             l = pn * pn
             ratio = si / (SN - 1)
             for blk, ada, kv in zip(var.blocks, adas, caches):
+                if self.use_kernel:
+                    self._block_native(blk, x, ada, kv, l, cur)
+                    continue
                 at = blk.attn
                 h = K.rownorm(x, a.norm_eps, layer=True, mscale=ada[:, 2 * C:3 * C], mshift=ada[:, 4 * C:5 * C],
                               rows_per_group=l)
@@ -503,7 +532,7 @@ class VARClassGenerator:
 
     def __init__(self, model_depth: int = 16, device: str = "cuda:0", DTYPE: torch.dtype = torch.float16,
                  arch: Optional[VARArch] = None, num_classes: int = 1000, weight_seed: int = 0,
-                 vae_chunk: int = 16):
+                 vae_chunk: int = 16, native_attention: bool = True):
         if arch is None:
             if model_depth not in {16, 20, 24, 30}:
                 raise ValueError("model_depth must be one of {16, 20, 24, 30}")
@@ -523,7 +552,7 @@ class VARClassGenerator:
         self.transformer = self.var
         self.vae_chunk = vae_chunk
         self.ctx = PopulationContext()
-        self.infer = VARPopulationInfer(self.var, self.vae)
+        self.infer = VARPopulationInfer(self.var, self.vae, use_kernel=native_attention)
 
     def _cast(self):
         """Frozen transformer linears bf16 (MFMA operands); VQVAE decoder bf16 channels-last."""

@@ -318,6 +318,18 @@ int eggroll_qk_norm_rope_kv(void* x, int64_t ldx, int64_t rows, int32_t heads, i
                             const void* w, const float* cos_tab, const float* sin_tab, int64_t tab_rows,
                             const float* hscale, void* out, int64_t out_bs, int64_t out_ld, int64_t rows_per_seq,
                             int64_t row0, const void* vin, int64_t ldv, void* vout, void* stream);
+/* q / k L2 normalisation, per-head q scale and KV-cache append at head dim 64, one launch, on the rows of one
+ * fused qkv GEMM output (VAR's attn_l2_norm attention).  q, k, v: bf16 [rows, >= heads*64] with their own row
+ * strides (multiples of 8), 16-byte aligned, head h at columns 64 h; any of them may be NULL (that part is absent).
+ *   q: y = x / max(|x|_2, eps) * qscale[h] per (row, head), in place; qscale fp32 [heads] or NULL (1)
+ *   k: y = x / max(|x|_2, eps), written to kout[(r / rows_per_seq) * out_bs + (row0 + r % rows_per_seq) * out_ld
+ *      + 64 h] (eggroll_qk_norm_rope_kv's cache addressing), or in place when kout is NULL
+ *   v: copied to vout at the same position (v and vout come together).
+ * fp32 math with a true division (F.normalize(x.float(), dim=-1).mul_(scale)), one bf16 rounding; an all-zero
+ * head stays zero for eps > 0.  head_dim must be 64; bad geometry or alignment is refused before the launch.  */
+int eggroll_qk_l2norm_kv(void* q, int64_t ldq, void* k, int64_t ldk, const void* v, int64_t ldv, int64_t rows,
+                         int32_t heads, int32_t head_dim, float eps, const float* qscale, void* kout, void* vout,
+                         int64_t out_bs, int64_t out_ld, int64_t rows_per_seq, int64_t row0, void* stream);
 /* The same row normalisation with dtype options: x_f32 = 1: fp32 input x (the fp32 residual stream of
  * the Sana blocks); mod_f32 = 1: fp32 modulation vectors (the fp32 AdaLN modulation); res_f32 = 1: fp32
  * res; out_f32 = 1: fp32 output (the DC-AE fp32 residual stream, out = norm(x)·w + b + res, may alias
@@ -501,10 +513,12 @@ int64_t eggroll_group_norm_workspace_bytes(int64_t B, int64_t HW, int32_t C, int
 int eggroll_group_norm_nhwc(const void* x, int64_t B, int64_t HW, int32_t C, int32_t G, float eps, const void* w,
                             const void* bias, int32_t act, void* y, void* workspace, void* stream);
 
-/* Flash attention, head dim 128, no mask (Z-Image self-attention, Infinity's attention over its KV cache):
+/* Flash attention, head_dim 128 or 64, no mask (Z-Image self-attention; Infinity's and VAR's attention over
+ * their KV caches):
  *   o[b,n,h,:] = softmax_j(scale * q[b,n,h,:] . k[b,j,h,:]) @ v[b,:,h,:],  n < Nq, j < Lk
- * q / k / v / o bf16, element (b, row, h, d) at X[b * X_bs + row * ldX + h * 128 + d] (a KV cache read in
- * place through its batch stride).  Online softmax in fp32, P rounded to bf16 for the PV MFMA.         */
+ * q / k / v / o bf16, element (b, row, h, d) at X[b * X_bs + row * ldX + h * head_dim + d] (a KV cache read in
+ * place through its batch stride; rows >= Lk are never read).  Online softmax in fp32, P rounded to bf16 for
+ * the PV MFMA.  Any other head_dim is refused before any launch.                                        */
 int eggroll_flash_attention(const void* q, int64_t q_bs, int64_t ldq, const void* k, int64_t k_bs, int64_t ldk,
                             const void* v, int64_t v_bs, int64_t ldv, int64_t B, int64_t heads, int64_t Nq,
                             int64_t Lk, int64_t head_dim, float scale, void* o, int64_t o_bs, int64_t ldo,

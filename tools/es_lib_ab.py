@@ -21,6 +21,8 @@ from hyperscalees_t2i_amd.sana import sana_lora_shapes  # noqa: E402
 def bind(path):
     lib = ctypes.CDLL(str(Path(path).resolve()))
     for name, (res, args) in _lib.SIGNATURES.items():
+        if not hasattr(lib, name):   # an older build: the entry points added since are not in it
+            continue
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = res, args
     return lib
