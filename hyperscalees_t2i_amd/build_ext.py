@@ -17,8 +17,8 @@ CSRC = PKG / "csrc"
 BUILD = PKG / "_build"
 LIB = BUILD / "libeggroll.so"
 # the translation units of libeggroll: the one list (_lib.SOURCE_FILES and the tools derive theirs from it)
-SOURCES = ["eggroll_es.hip", "eggroll_lora.hip", "eggroll_conv.hip", "eggroll_model.hip", "eggroll_attn.hip",
-           "eggroll_gguf.hip", "eggroll_image.hip"]
+SOURCES = ["eggroll_es.hip", "eggroll_lora.hip", "eggroll_conv.hip", "eggroll_nhwc.hip", "eggroll_norm.hip",
+           "eggroll_qk.hip", "eggroll_linattn.hip", "eggroll_attn.hip", "eggroll_gguf.hip", "eggroll_image.hip"]
 ARCH = "gfx950"
 
 

@@ -5,6 +5,7 @@
 #include <stdio.h>
 #include <string>
 #include <type_traits>
+#include <utility>
 
 #include "../../include/eggroll.h"
 
@@ -30,6 +31,14 @@ void set_error(const char* fmt, ...);
     } while (0)
 
 inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
+
+// Host side, run-time value -> std::integral_constant: calls f with the constant of Vs equal to v; false when
+// v is none of them.  The list at a call is the set of kernel instances that call can launch.
+template <int... Vs, class F>
+static bool dispatch_int(int v, std::integer_sequence<int, Vs...>, F&& f) {
+    return ((v == Vs ? (f(std::integral_constant<int, Vs>{}), true) : false) || ...);
+}
+using Flag01 = std::integer_sequence<int, 0, 1>;  // a bool template argument
 
 // ---- wave (64-lane) reductions -------------------------------------------------------
 __device__ __forceinline__ float wave_sum(float v) {

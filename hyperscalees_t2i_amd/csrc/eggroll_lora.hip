@@ -1228,12 +1228,7 @@ __global__ __launch_bounds__(512, 1) void k_lora_gemm8f(
     store_tile_t(acc, smem, wave, lane, m0, n0, wm * 128, wn * 64, M, N, Y, ldy);
 }
 
-// Run-time value -> std::integral_constant: calls f with the constant of Vs equal to v; false when
-// v is none of them.  The lists below are the instantiated kernels.
-template <int... Vs, class F>
-static bool dispatch_int(int v, std::integer_sequence<int, Vs...>, F&& f) {
-    return ((v == Vs ? (f(std::integral_constant<int, Vs>{}), true) : false) || ...);
-}
+// The instantiated kernels (dispatch_int, common.h).
 using RanksAll = std::integer_sequence<int, 0, 1, 2, 3, 4, 8, 16>;
 using RanksMF = std::integer_sequence<int, 0, 1, 2>;  // the MFMA-addend path
 using EpiOps = std::integer_sequence<int, EPI_NONE, EPI_SILU, EPI_RES, EPI_GATED, EPI_RES32, EPI_GATED32, EPI_GELU,

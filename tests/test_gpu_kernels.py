@@ -459,7 +459,7 @@ def test_resid_layernorm_vs_torch(dev, rows, C, strided, add):
                                          + 0.5).to(dev)[:, 1:])
     err = (out.float() - ref).abs()
     assert bool((err <= 2.0 ** -8 * ref.abs() + 1e-5).all()), float(err.max())
-@pytest.mark.parametrize("C", [32, 128, 256, 512, 1024, 2240, 2560, 4096])
+@pytest.mark.parametrize("C", [32, 128, 256, 512, 1024, 2048, 2240, 2560, 4096])
 @pytest.mark.parametrize("mode", ["rms_w_b_res", "rms_relu", "layer_adaln"])
 def test_rownorm_vs_torch(dev, C, mode):
     g = torch.Generator().manual_seed(C)
@@ -698,8 +698,14 @@ def test_linear_attention_head_pairs_bitexact(dev, B, N, heads, relu):
     within bf16 rounding.  N >= 8192 takes the 16-tile-per-wave output pass; 16500 ends on partial token
     chunks and a partial output block."""
     g = torch.Generator().manual_seed(B * N + heads)
+    flat = torch.randn(B * N, 3 * heads * 32, generator=g).to(torch.bfloat16).to(dev)
+    _linear_attention_heads_bitexact(flat, B, N, heads, relu)
+
+
+def _linear_attention_heads_bitexact(flat, B, N, heads, relu):
+    """flat: planar [Q | K | V] rows [B*N, 3 * heads * 32] bf16.  Each head's output of the all-heads call equals a
+    one-head call on that head's columns bit for bit, and the fp32 restatement holds within bf16 rounding."""
     inner = heads * 32
-    flat = torch.randn(B * N, 3 * inner, generator=g).to(torch.bfloat16).to(dev)
     if not relu:
         flat = flat.abs()   # keep the denominator away from 0 (as Sana's post-ReLU keys)
     q, k, v = flat, flat[:, inner:], flat[:, 2 * inner:]
@@ -711,6 +717,18 @@ def test_linear_attention_head_pairs_bitexact(dev, B, N, heads, relu):
     ref = _linear_attention_ref(q[:, :inner].reshape(sh), k[:, :inner].reshape(sh), v[:, :inner].reshape(sh), relu)
     rel = ((got.float().view(sh) - ref).norm() / ref.norm()).item()
     assert rel < 8e-3, rel
+
+
+@pytest.mark.parametrize("B,N,heads,relu", [(64, 300, 64, False), (64, 770, 64, True), (64, 300, 33, False)])
+def test_linear_attention_fold_bitexact(dev, B, N, heads, relu):
+    """Few chunks per head (nchunk <= LA_FOLD_MAX = 4) on >= 2048 head (pair) blocks: the kv pass with the chunk
+    reduction folded in (k_la_kv_fold).  The one-head comparison calls have 64 blocks and take k_la_kv +
+    k_la_reduce, so the bitwise check pins fold against unfold.  (64, 300, 64): head pairs (8192 per-head
+    blocks), 2 chunks with a 44-token tail; (64, 770, 64): 4 chunks, a 2-token tail; (64, 300, 33): an odd head
+    count, one head per block (4224 blocks < 8192, 2112 >= 2048)."""
+    g = torch.Generator(device=dev).manual_seed(B * N + heads)   # 0.2-0.6 GB of inputs: drawn on the device
+    flat = torch.randn(B * N, 3 * heads * 32, device=dev, generator=g).to(torch.bfloat16)
+    _linear_attention_heads_bitexact(flat, B, N, heads, relu)
 
 
 @pytest.mark.parametrize("B,H,W,C,ks", [(2, 9, 13, 96, 5), (1, 64, 64, 384, 5), (2, 20, 40, 64, 3)])

@@ -14,14 +14,14 @@ from pathlib import Path
 import pytest
 
 import isa_scan
+from hyperscalees_t2i_amd.build_ext import SOURCES
 
 BUILD = Path(__file__).resolve().parent.parent / "hyperscalees_t2i_amd" / "_build"
 ALLOWED = re.compile(r"^_ZN7eggroll8k_update")
 
 
 @pytest.mark.skipif(not isa_scan.tools_present(), reason="ROCm LLVM tools absent")
-@pytest.mark.parametrize("unit", ["eggroll_es", "eggroll_lora", "eggroll_conv", "eggroll_model",
-                                  "eggroll_attn"])
+@pytest.mark.parametrize("unit", [Path(s).stem for s in SOURCES])
 def test_no_unguarded_scalar_data_loads(unit):
     obj = BUILD / f"{unit}.o"
     if not obj.exists():

@@ -1,7 +1,7 @@
 """Kernel-by-kernel comparison of two builds' gfx950 assembly (the `*gfx950*.s` files that
 `hipcc --save-temps -c` leaves behind), for refactors that must not change the generated code.
 
-    python tools/isa_compare.py --old DIR --new DIR --out profiles/NAME.json
+    python tools/isa_compare.py --old DIR --new DIR --out profiles/NAME.json [--brief]
 
 One row per kernel, one line each: old and new name, the code-object notes (VGPR / AGPR / SGPR counts,
 spills, private segment and LDS bytes), the instruction count and a SHA-256 of the instructions with symbol names and
@@ -70,6 +70,8 @@ def main():
     ap.add_argument("--old", type=Path, required=True)
     ap.add_argument("--new", type=Path, required=True)
     ap.add_argument("--out", type=Path, required=True)
+    ap.add_argument("--brief", action="store_true",
+                    help="a kernel whose notes, count and hash are all equal gets the row [name, instructions, sha256[:16]]")
     a = ap.parse_args()
     old, new = load(a.old), load(a.new)
     table, bad, cols = [], [], (*NOTES, "instructions", "sha256")
@@ -91,7 +93,12 @@ def main():
     differ = [r["kernel"] for r in table if not r["hash_equal"]]
     # one row per line; new_name / new are null where they equal old_name / old
     head = {"kernels": len(table), "problems": bad, "hash_differs": len(differ), "columns": cols}
-    a.out.write_text("{" + json.dumps(head)[1:-1] + ',\n"rows": [\n' + ",\n".join(json.dumps(r) for r in table) + "\n]}\n")
+    lines = [json.dumps(r) for r in table]
+    if a.brief:   # equal kernels first, four to a line; then the full rows of the rest
+        same = [r for r in table if r["new"] is None and r["new_name"] is None]
+        short = [json.dumps([r["kernel"], r["old"][-2], r["old"][-1][:16]]) for r in same]
+        lines = [", ".join(short[i:i + 4]) for i in range(0, len(short), 4)] + [json.dumps(r) for r in table if r not in same]
+    a.out.write_text("{" + json.dumps(head)[1:-1] + ',\n"rows": [\n' + ",\n".join(lines) + "\n]}\n")
     print(f"{len(table)} kernels matched, {len(differ)} differ in hash, {len(bad)} problems")
     for b in bad:
         print("  " + b)
