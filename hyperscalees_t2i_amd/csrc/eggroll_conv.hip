@@ -441,17 +441,18 @@ __global__ __launch_bounds__(512, 1) void k_conv3x3_gemm8(const unsigned short* 
 // phases of 16 MFMAs (A fragments 0-3, then 4-7, against the same 4 B fragments) with the p8 wave-
 // group stagger; all DMA waits are counted vmcnt (compile-time per tap, see hc_wait_n).
 // ------------------------------------------------------------------------------------
-// PAD: halo rows HS = HW2 rounded up to 8 pixels (the pad columns are zero-filled, never read).  The
-// fragment swizzle keys on bit 2 of the halo pixel index; with HS % 8 == 0 a tap's row shift dy (HS
+// Halo rows are padded: HS = HW2 rounded up to 8 pixels (the pad columns are zero-filled, never read).
+// The fragment swizzle keys on bit 2 of the halo pixel index; with HS % 8 == 0 a tap's row shift dy (HS
 // pixels) leaves that bit alone, so a fragment needs one swizzled address per column shift dx and the
 // row shift is the ds_read immediate (3 addresses per fragment instead of 9: 24 VGPRs instead of 72).
-template <int WMW, int WNW = 8 / WMW, bool PAD = true>
+template <int WMW, int WNW = 8 / WMW>
 struct HC {
+    static_assert(WMW * WNW == 8, "one 8-wave workgroup per CU");
     static constexpr int WM_ = WMW, WN_ = WNW;
     static constexpr int NW = WMW * WNW, BM = WMW * 128, BN = WNW * 64;  // waves, tile
     static constexpr int TH = 16, TWD = BM / TH;                 // output pixels of a tile
     static constexpr int HW2 = TWD + 2;                          // halo pixels per row
-    static constexpr int HS = PAD ? (HW2 + 7) / 8 * 8 : HW2;     // halo row stride in LDS (pixels)
+    static constexpr int HS = (HW2 + 7) / 8 * 8;                 // halo row stride in LDS (pixels)
     static constexpr int HP = (TH + 2) * HS;                     // halo pixel slots
     static constexpr int NPW = (HP + 16 * NW - 1) / (16 * NW);  // halo pieces (16 px x 64 B) per wave
     static constexpr int HALO = NPW * NW * 1024;
@@ -559,18 +560,17 @@ __device__ __forceinline__ void store_tile_rows(f32x4 (&acc)[8][4], char* smem, 
 }
 
 // WMW x WNW waves: (4, 2) 512 x 128 and (2, 4) 256 x 256 tiles run one 8-wave workgroup per CU
-// with the two wave groups staggered by a barrier (as the p8 kernels); (2, 2) 256 x 128 runs two
-// 4-wave workgroups per CU (80 KiB LDS each), which overlap each other's prologue and epilogue.
-template <int ACT, bool NORM, int WMW, int WNW, bool PAD = true>
-__global__ __launch_bounds__(64 * WMW * WNW, 8 / (WMW * WNW)) void k_conv3x3_halo(const unsigned short* __restrict__ X,
+// with the two wave groups staggered by a barrier (as the p8 kernels).
+template <int ACT, bool NORM, int WMW, int WNW>
+__global__ __launch_bounds__(512, 1) void k_conv3x3_halo(const unsigned short* __restrict__ X,
                                                          const unsigned short* __restrict__ Wt,
                                                          const unsigned short* __restrict__ bias, int H, int W,
                                                          int Cin, int N, int tiles_n, unsigned short* __restrict__ Y,
                                                          float eps = 0.0f, const unsigned short* __restrict__ nw = nullptr,
                                                          const unsigned short* __restrict__ nb = nullptr,
                                                          const unsigned short* __restrict__ res = nullptr) {
-    using G = HC<WMW, WNW, PAD>;
-    static_assert(halo_smem_bytes<G, NORM>() * (8 / G::NW) <= 160 * 1024, "LDS per CU");
+    using G = HC<WMW, WNW>;
+    static_assert(halo_smem_bytes<G, NORM>() <= 160 * 1024, "LDS per CU");
     __shared__ __attribute__((aligned(16))) char smem[halo_smem_bytes<G, NORM>()];
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave / WNW, wn = wave % WNW;
@@ -606,25 +606,20 @@ __global__ __launch_bounds__(64 * WMW * WNW, 8 / (WMW * WNW)) void k_conv3x3_hal
         const int c = (lane & 3) ^ (((n >> 2) & 1) << 1);
         boff[i] = (uint32_t)(((n0 + n) * K + c * 8) * 2);
     }
-    // fragment reads: A row f of the wave at tap (0,0) as a logical halo byte (!PAD: swizzled per tap);
-    // PAD: the swizzled byte of A row f at column shift dx (row shift dy = immediate dy * HS * 64)
-    uint32_t la[8];
-    uint32_t ad[PAD ? 8 : 1][PAD ? 3 : 1];
+    // fragment reads: A row f of the wave at tap (0,0) as a logical halo byte la, then the swizzled
+    // byte of A row f at column shift dx (row shift dy = immediate dy * HS * 64)
+    uint32_t ad[8][3];
 #pragma unroll
     for (int f = 0; f < 8; ++f) {
         const int m = wm * 128 + 16 * f + (lane & 15);
         const int ty = m / G::TWD, tx = m % G::TWD;
-        la[f] = (uint32_t)((ty * G::HS + tx) * 64 + (lane >> 4) * 16);
-        if constexpr (PAD)
+        const uint32_t la = (uint32_t)((ty * G::HS + tx) * 64 + (lane >> 4) * 16);
 #pragma unroll
-            for (int dx = 0; dx < 3; ++dx) ad[f][dx] = hc_swz(la[f] + dx * 64);
+        for (int dx = 0; dx < 3; ++dx) ad[f][dx] = hc_swz(la + dx * 64);
     }
     auto afrag = [&](const char* hb, int f, auto T_) -> bf16x8 {
         constexpr int T = decltype(T_)::value;
-        if constexpr (PAD)
-            return *reinterpret_cast<const bf16x8*>(hb + ad[f][T % 3] + (T / 3) * G::HS * 64);
-        else
-            return *reinterpret_cast<const bf16x8*>(hb + hc_swz(la[f] + (uint32_t)(((T / 3) * G::HS + T % 3) * 64)));
+        return *reinterpret_cast<const bf16x8*>(hb + ad[f][T % 3] + (T / 3) * G::HS * 64);
     };
     const uint32_t lb = hc_swz((uint32_t)((wn * 64 + (lane & 15)) * 64 + (lane >> 4) * 16));
 
@@ -665,7 +660,7 @@ __global__ __launch_bounds__(64 * WMW * WNW, 8 / (WMW * WNW)) void k_conv3x3_hal
     wait_vm<(G::D - 1) * G::NBW>();  // halo 0 + weights of K-step 0
     P8_BAR();
     EGG_STAMP(1);
-    if (G::NW == 8 && grp8 == 1) P8_BAR();
+    if (grp8 == 1) P8_BAR();
 
     auto slice = [&](int s, auto NEXT_, auto LAST_) {
         constexpr bool NEXT = decltype(NEXT_)::value, LAST = decltype(LAST_)::value;
@@ -711,7 +706,7 @@ __global__ __launch_bounds__(64 * WMW * WNW, 8 / (WMW * WNW)) void k_conv3x3_hal
     };
     for (int s = 0; s < S - 1; ++s) slice(s, std::true_type{}, std::false_type{});
     slice(S - 1, std::false_type{}, std::true_type{});
-    if (G::NW == 8 && grp8 == 0) P8_BAR();
+    if (grp8 == 0) P8_BAR();
     EGG_STAMP(2);
     wait_vm<0>();
     __syncthreads();
@@ -741,301 +736,6 @@ __global__ __launch_bounds__(64 * WMW * WNW, 8 / (WMW * WNW)) void k_conv3x3_hal
     EGG_STAMP_RT(7);
 }
 
-// ------------------------------------------------------------------------------------
-// Multi-tile halo conv (eggroll_conv_nhwc_sel kernel 4): one workgroup runs MT vertically stacked
-// tiles of one image column as ONE K-step stream, so the next tile's slice-0 halo and first D weight
-// K-steps stream in during the current tile's last slice exactly as a middle slice streams slice s+1
-// — the per-tile prologue (the first halo + weights, ~11 % of a 128-channel tile) is paid once per
-// MT tiles.  What that needs:
-//   * the C tile goes out through a DEDICATED wave-private 4-KiB staging region, 32 rows at a time
-//     (after the ring: nothing the in-flight DMAs write), so the epilogue overlaps them;
-//   * the next tile's halo offsets / buffer base are recomputed in place right before the last slice
-//     (the current tile's are dead by then): no extra state is carried through the MFMA loop;
-//   * the first two counted waits of the next tile target weights issued BEFORE the epilogue, so
-//     they add the epilogue's 16 C-tile stores (a lower bound of its vector-memory ops: waiting for
-//     fewer younger ops than exist only over-waits) instead of draining the stores.
-// Same MFMA sequence per tile, same epilogue arithmetic: bit-identical to kernel 2.
-// ------------------------------------------------------------------------------------
-constexpr int HMT_EPI_STORES = 16;  // store_tile_rows_c32: 4 passes x 4 16-B stores per lane
-
-// RES: + the residual rows (the same 16-B row segments as the stores), streamed one pass ahead: the
-// caller loads pass 0's four rows (rv) before its norm math, pass p + 1's are issued while pass p goes
-// through LDS — 2 x 16 registers instead of all 64 next to the accumulators.
-template <int ACT, class RowOf, bool RES = false>
-__device__ __forceinline__ void store_tile_rows_c32(f32x4 (&acc)[8][4], char* ctile, int lane, int rbase, int col0,
-                                                    unsigned short* __restrict__ Y, int64_t ldy, RowOf row_of,
-                                                    const unsigned short* __restrict__ res, u16x8 (&rv)[4]) {
-    constexpr int ROWB = 128, SLOTS = 8;
-    const int r_l = lane & 15, c_l = (lane >> 4) * 4;
-#pragma unroll
-    for (int p = 0; p < 4; ++p) {
-        u16x8 rn[4];
-        if constexpr (RES) {
-            if (p < 3) load_res_rows<0, 4>(rn, res, lane, rbase + (p + 1) * 32, col0, ldy, row_of);
-        }
-#pragma unroll
-        for (int ii = 0; ii < 2; ++ii) {
-            const int rr = ii * 16 + r_l;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int cc = j * 16 + c_l;
-                const int slot = (cc >> 3) ^ (rr & (SLOTS - 1));
-                u16x4 o;
-#pragma unroll
-                for (int e = 0; e < 4; e += 2) {
-                    f32x2 v = {acc[2 * p + ii][j][e], acc[2 * p + ii][j][e + 1]};
-                    if constexpr (ACT == 1) v = silu2(v);
-                    o[e] = f32_to_bf16(v.x);
-                    o[e + 1] = f32_to_bf16(v.y);
-                }
-                *reinterpret_cast<u16x4*>(ctile + rr * ROWB + slot * 16 + (cc & 7) * 2) = o;
-            }
-        }
-        __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0): this pass's LDS writes done
-        u16x8 v[4];
-#pragma unroll
-        for (int it = 0; it < 4; ++it) {
-            const int rr = it * 8 + (lane >> 3), sl = lane & 7;
-            v[it] = *reinterpret_cast<const u16x8*>(ctile + rr * ROWB + ((sl ^ (rr & (SLOTS - 1))) << 4));
-        }
-        __builtin_amdgcn_s_waitcnt(0xC07F);  // reads done before the next pass overwrites the region
-#pragma unroll
-        for (int it = 0; it < 4; ++it) {
-            const int rr = it * 8 + (lane >> 3);
-            if constexpr (RES) {
-#pragma unroll
-                for (int u = 0; u < 8; ++u) v[it][u] = f32_to_bf16(bf16_to_f32(v[it][u]) + bf16_to_f32(rv[it][u]));
-            }
-            *reinterpret_cast<u16x8*>(Y + row_of(rbase + p * 32 + rr) * ldy + col0 + (lane & 7) * 8) = v[it];
-        }
-        if constexpr (RES) {
-            if (p < 3)
-#pragma unroll
-                for (int it = 0; it < 4; ++it) rv[it] = rn[it];
-        }
-    }
-}
-
-template <class G, bool NORM>
-constexpr int halo_mt_smem_bytes() {
-    static_assert(!NORM || G::BM * G::WN_ * 4 <= G::HALO, "RMSNorm row sums go to halo buffer 1");
-    return G::LDS + G::NW * 4096;
-}
-
-template <int ACT, bool NORM, int WMW, int WNW>
-__global__ __launch_bounds__(64 * WMW * WNW, 1) void k_conv3x3_halo_mt(const unsigned short* __restrict__ X,
-                                                                      const unsigned short* __restrict__ Wt,
-                                                                      const unsigned short* __restrict__ bias, int H,
-                                                                      int W, int Cin, int N, int tiles_n, int mt,
-                                                                      unsigned short* __restrict__ Y, float eps = 0.0f,
-                                                                      const unsigned short* __restrict__ nw = nullptr,
-                                                                      const unsigned short* __restrict__ nb = nullptr,
-                                                                      const unsigned short* __restrict__ res = nullptr) {
-    using G = HC<WMW, WNW>;
-    static_assert(G::NW == 8, "one 8-wave workgroup per CU");
-    static_assert(halo_mt_smem_bytes<G, NORM>() <= 160 * 1024, "LDS per CU");
-    __shared__ __attribute__((aligned(16))) char smem[halo_mt_smem_bytes<G, NORM>()];
-    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wm = wave / WNW, wn = wave % WNW;
-    const int grp8 = wave >> 2;
-    char* const ctile = smem + G::LDS + wave * 4096;
-    // RMSNorm row sums: halo buffer 1 (slice S-1's, S even), free between a tile's last MFMA and the next
-    // tile's first slice-1 halo DMA (the prefetch only writes buffer 0 and ring slots 0..D-1)
-    float* const red = reinterpret_cast<float*>(smem + G::HALO);
-    // XCD-contiguous group ranges; a group = mt vertically stacked tiles of one column, horizontally
-    // neighbouring groups (sharing halo columns) adjacent, the N-tiles of one group adjacent
-    const int grp = xcd_remap(blockIdx.x, gridDim.x);
-    const int gm = grp / tiles_n, tn = grp - gm * tiles_n;
-    const int n0 = tn * G::BN;
-    const int tpr = W / G::TWD, bgs = (H / G::TH) / mt;  // tiles per row band, band groups per image
-    const int xt = gm % tpr, gr = gm / tpr;
-    const int img = gr / bgs, bg = gr - img * bgs;
-    const int x0 = xt * G::TWD;
-    const int K = 9 * Cin, S = Cin / 32;
-    EGG_STAMP_RT(6);
-    EGG_STAMP(0);
-
-    // halo DMA of tile row band y0: piece i*8 + wave holds halo pixels 16p .. 16p+15; out-of-image
-    // pixels (and the pad past HP) read as zeros through an out-of-range offset
-    uint32_t hoff[G::NPW];
-    __amdgpu_buffer_rsrc_t rX;
-    auto halo_setup = [&](int y0, int ln) {
-#pragma unroll
-        for (int i = 0; i < G::NPW; ++i) {
-            const int hp = (i * G::NW + wave) * 16 + (ln >> 2);
-            const int c = (ln & 3) ^ (((hp >> 2) & 1) << 1);
-            const int hy = hp / G::HS, hx = hp - hy * G::HS;
-            const int y = y0 - 1 + hy, x = x0 - 1 + hx;
-            const bool ok = hp < G::HP && hx < G::HW2 && y >= 0 && y < H && x >= 0 && x < W;
-            hoff[i] = ok ? (uint32_t)(((hy * W + hx) * Cin + c * 8) * 2) : 0x80000000u;
-        }
-        const int64_t pb = ((int64_t)img * H + y0 - 1) * W + (x0 - 1);  // halo pixel (0, 0)
-        const uint64_t xbu = (uint64_t)(X + pb * Cin);
-        const unsigned short* xb = (const unsigned short*)(
-            ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(xbu >> 32)) << 32) |
-            (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)xbu));
-        rX = __builtin_amdgcn_make_buffer_rsrc((void*)xb, (short)0, 0x7fffffff, 0x00020000);
-    };
-    uint32_t boff[G::NBW];
-#pragma unroll
-    for (int i = 0; i < G::NBW; ++i) {
-        const int n = (i * G::NW + wave) * 16 + (lane >> 2);
-        const int c = (lane & 3) ^ (((n >> 2) & 1) << 1);
-        boff[i] = (uint32_t)(((n0 + n) * K + c * 8) * 2);
-    }
-    // A-fragment addresses (HC PAD layout: one swizzled byte per fragment and column shift dx, the row
-    // shift is the ds_read immediate); set per tile from an opaque copy of the lane id so nothing derived
-    // from them is carried through the epilogue
-    uint32_t ad[8][3];
-    auto make_la = [&](int ln) {
-#pragma unroll
-        for (int f = 0; f < 8; ++f) {
-            const int m = wm * 128 + 16 * f + (ln & 15);
-            const int ty = m / G::TWD, tx = m % G::TWD;
-            const uint32_t L = (uint32_t)((ty * G::HS + tx) * 64 + (ln >> 4) * 16);
-#pragma unroll
-            for (int dx = 0; dx < 3; ++dx) ad[f][dx] = hc_swz(L + dx * 64);
-        }
-    };
-    const uint32_t lb = hc_swz((uint32_t)((wn * 64 + (lane & 15)) * 64 + (lane >> 4) * 16));
-    const __amdgpu_buffer_rsrc_t rW = __builtin_amdgcn_make_buffer_rsrc((void*)Wt, (short)0, 0x7fffffff, 0x00020000);
-
-    auto issue_b = [&](int sl, int tap, int slot) {
-        const int so = __builtin_amdgcn_readfirstlane((tap * Cin + sl * 32) * 2);
-        char* dst = smem + G::RB + slot * G::BSLOT;
-#pragma unroll
-        for (int i = 0; i < G::NBW; ++i) {
-            const uint32_t v = boff[i];
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rW, (lds_void*)(dst + (i * G::NW + wave) * 1024), 16, v, so, 0, 0);
-        }
-    };
-    auto issue_h = [&](auto I, int sl) {
-        constexpr int i = decltype(I)::value;
-        const uint32_t v = hoff[i];
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rX, (lds_void*)(smem + (sl & 1) * G::HALO + (i * G::NW + wave) * 1024),
-                                                 16, v, sl * 64, 0, 0);
-    };
-
-    f32x4 acc[8][4];
-    bf16x8 a[4], b[4];
-    const int yb = bg * mt * G::TH;  // first tile's row band
-    // a tile's slice-0 halo + first D weight K-steps: for tile 0 here, for tile t+1 right after tile
-    // t's last MFMA (before its epilogue), into LDS the epilogue does not touch
-    auto prefetch = [&](int y0, int ln) {
-        halo_setup(y0, ln);
-        hc_static_for<0, G::NPW>([&](auto I) { issue_h(I, 0); });
-#pragma unroll
-        for (int d = 0; d < G::D; ++d) issue_b(0, d, d);
-    };
-    prefetch(yb, lane);
-
-    // Every tile restarts the K-step count at 0 (ring slot = K-step & 3; 9 S K-steps per tile, the ring
-    // is drained at the tile boundary).  epi: an epilogue's >= HMT_EPI_STORES vector-memory ops sit
-    // between this tile's first D weight K-steps and the rest, so the waits that target K-steps 0..D-1
-    // (the tile's first wait and taps 0 .. D-2 of slice 0) count them as younger ops.
-    auto slice = [&](int s, bool epi, auto NEXT_, auto LAST_) {
-        constexpr bool NEXT = decltype(NEXT_)::value, LAST = decltype(LAST_)::value;
-        const char* hb = smem + (s & 1) * G::HALO;
-        hc_static_for<0, 9>([&](auto T_) {
-            constexpr int T = decltype(T_)::value;
-            constexpr int DY = (T / 3) * G::HS * 64;
-            const int k = s * 9 + T;
-            const char* bs = smem + G::RB + (k & (G::NBUF - 1)) * G::BSLOT;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) b[j] = *reinterpret_cast<const bf16x8*>(bs + lb + j * 1024);
-#pragma unroll
-            for (int u = 0; u < 4; ++u) a[u] = *reinterpret_cast<const bf16x8*>(hb + ad[u][T % 3] + DY);
-            if constexpr (!LAST || T + G::D < 9) {
-                if constexpr (T + G::D < 9) issue_b(s, T + G::D, (k + G::D) & (G::NBUF - 1));
-                else issue_b(s + 1, T + G::D - 9, (k + G::D) & (G::NBUF - 1));
-            }
-            P8_LGKM0();
-            P8_BAR();
-            __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-            for (int u = 0; u < 4; ++u)
-#pragma unroll
-                for (int j = 0; j < 4; ++j) acc[u][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(b[j], a[u], acc[u][j], 0, 0, 0);
-            __builtin_amdgcn_s_setprio(0);
-            P8_BAR();
-#pragma unroll
-            for (int u = 0; u < 4; ++u) a[u] = *reinterpret_cast<const bf16x8*>(hb + ad[4 + u][T % 3] + DY);
-            if constexpr (NEXT && T < G::NPW) issue_h(std::integral_constant<int, T>{}, s + 1);
-            if constexpr (!(LAST && T == 8)) {
-                if constexpr (NEXT && T < G::D - 1) {  // only slice 0 can follow an epilogue
-                    if (epi) wait_vm<hc_wait_n<G, T, NEXT, LAST>() + HMT_EPI_STORES>();
-                    else wait_vm<hc_wait_n<G, T, NEXT, LAST>()>();
-                } else {
-                    wait_vm<hc_wait_n<G, T, NEXT, LAST>()>();
-                }
-            }
-            P8_LGKM0();
-            P8_BAR();
-            __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-            for (int u = 0; u < 4; ++u)
-#pragma unroll
-                for (int j = 0; j < 4; ++j)
-                    acc[4 + u][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(b[j], a[u], acc[4 + u][j], 0, 0, 0);
-            __builtin_amdgcn_s_setprio(0);
-            P8_BAR();
-        });
-    };
-
-#pragma unroll 1
-    for (int t = 0; t < mt; ++t) {
-        const int y0 = yb + t * G::TH;
-        int ln = lane;
-        asm volatile("" : "+v"(ln));
-        make_la(ln);
-        if (t > 0) halo_setup(y0, ln);  // this tile's halo offsets again (not kept through the epilogue)
-        if (t == 0) wait_vm<(G::D - 1) * G::NBW>();  // halo 0 + weights of K-step 0
-        else wait_vm<(G::D - 1) * G::NBW + HMT_EPI_STORES>();
-        P8_BAR();
-        if (t == 0) EGG_STAMP(1);
-        if (grp8 == 1) P8_BAR();  // wave-group stagger, realigned before the epilogue
-#pragma unroll
-        for (int i = 0; i < 8; ++i)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll 1
-        for (int s = 0; s < S - 1; ++s) slice(s, t > 0 && s == 0, std::true_type{}, std::false_type{});
-        slice(S - 1, false, std::false_type{}, std::true_type{});
-        if (grp8 == 0) P8_BAR();
-        if (t == 0) EGG_STAMP(2);
-        // everything lane-derived that the prefetch and the epilogue need is re-derived here from an opaque
-        // copy of the lane id: hoisted out of the tile loop it would be spilled, and a scratch reload
-        // waits vmcnt(0) — behind the next tile's prefetch DMAs, i.e. it serialises the two
-        int lne = lane;
-        asm volatile("" : "+v"(lne));
-        if (t + 1 < mt) {
-            // every wave has passed its last fragment read of this tile (the barrier above): halo
-            // buffer 0 and the ring are free for the next tile
-            prefetch(y0 + G::TH, lne);
-        }
-        const int64_t prow = ((int64_t)img * H + y0) * W + x0;  // output pixel of tile row 0
-        auto row_of = [&](int r) -> int64_t { return prow + (int64_t)(r / G::TWD) * W + (r % G::TWD); };
-        if (bias)
-            lora_mfma_addend<0>(acc, lne, 0, n0, wm * 128, wn * 64, bias, nullptr, nullptr, 0, 0, 0.0f, 1 << 30, 1 << 30,
-                                N);
-        if constexpr (NORM) {
-            u16x8 rv[4];  // pass 0's residual rows, in flight during the norm math
-            load_res_rows<0, 4>(rv, res, lne, wm * 128, n0 + wn * 64, N, row_of);
-            conv_rmsnorm_epilogue<1, WMW, WNW>(acc, red, wm, wn, lne, row_of, eps, nw, nb,
-                                               (const unsigned short*)nullptr);
-            store_tile_rows_c32<0, decltype(row_of), true>(acc, ctile, lne, wm * 128, n0 + wn * 64, Y, N, row_of, res,
-                                                          rv);
-        } else {
-            u16x8 rv0[4];
-            store_tile_rows_c32<ACT>(acc, ctile, lne, wm * 128, n0 + wn * 64, Y, N, row_of, nullptr, rv0);
-        }
-        if (t == 0) EGG_STAMP(3);
-    }
-    EGG_STAMP_DRAIN();
-    EGG_STAMP(5);
-    EGG_STAMP_RT(7);
-}
-
 }  // namespace eggroll
 
 using namespace eggroll;
@@ -1049,61 +749,104 @@ extern "C" int eggroll_debug_conv_stamps(unsigned long long* host, int64_t n) {
 }
 #endif
 
+// The arguments the conv kernels share, as the entry points got them (the RMSNorm tail's stay null without it).
+struct ConvArgs {
+    const void *x, *w, *bias;
+    int64_t B, H, W, Cin, N;
+    void* y;
+    float eps = 0.0f;
+    const void *nw = nullptr, *nb = nullptr, *res = nullptr;
+};
+
 // The halo-staged kernel takes 3x3 px-1 convs whose tiles are all full: H % 16 == 0, W % TWD == 0
 // (TWD = 32 for the 512 x 128 tile, 16 for 256 x 256), N % BN == 0: 512 x 128 (N == 128) or 256 x 256
-// (N % 256 == 0), one 8-wave workgroup per CU.  Variant v: 2 = padded halo rows (HC PAD), 3 = the
-// round-2 unpadded layout (A/B), 4 = multi-tile (padded).
-static bool halo_ok(int v, int64_t ks, int64_t px, int64_t H, int64_t W, int64_t Cin, int64_t N) {
-    (void)v;
+// (N % 256 == 0), one 8-wave workgroup per CU.
+static bool halo_ok(int64_t ks, int64_t px, int64_t H, int64_t W, int64_t Cin, int64_t N) {
     if (ks != 3 || px != 1 || H % 16 || 18 * (W + 2) * Cin * 2 >= (1ll << 31)) return false;  // 32-bit halo offsets
     if (N == 128) return W % HC<4>::TWD == 0;
     return N % 256 == 0 && W % HC<2>::TWD == 0;
 }
 
-// kernel 4 (multi-tile): tiles per workgroup = the largest of 4, 2, 1 dividing the row bands H / 16
-static int halo_mt_tiles(int64_t H) {
-    const int64_t bands = H / 16;
-    return bands % 4 == 0 ? 4 : bands % 2 == 0 ? 2 : 1;
+// The kernel selector of the _sel entry points (`fn` names the one called): 0 the halo kernel where halo_ok
+// and the tap-staged one elsewhere, 1 tap-staged, 2 halo (refused where it does not apply).
+static int conv_kernel_sel(const char* fn, int32_t kernel, int64_t ks, int64_t px, int64_t H, int64_t W, int64_t Cin,
+                           int64_t N, bool* halo) {
+    EGG_CHECK_ARG(kernel >= 0 && kernel <= 2, "%s: kernel must be 0 (auto), 1 (tap-staged) or 2 (halo) (got %d)", fn,
+                  kernel);
+    const bool hok = halo_ok(ks, px, H, W, Cin, N);
+    EGG_CHECK_ARG(kernel < 2 || hok, "%s: halo kernel 2 needs ks 3, px 1, H %% 16 == 0 and W, N multiples of the tile "
+                  "(see include/eggroll.h)", fn);
+    *halo = hok && kernel != 1;
+    return EGGROLL_OK;
 }
 
-template <int ACT, bool NORM, int WMW, int WNW>
-static void launch_halo_mt_t(const void* x, const void* w, const void* bias, int64_t B, int64_t H, int64_t W,
-                             int64_t Cin, int64_t N, void* y, float eps, const void* nw, const void* nb, const void* res,
-                             hipStream_t st) {
-    using G = HC<WMW, WNW>;
-    const int mt = halo_mt_tiles(H);
-    const int64_t groups = B * (H / 16 / mt) * (W / G::TWD), tn = N / G::BN;
-    hipLaunchKernelGGL((k_conv3x3_halo_mt<ACT, NORM, WMW, WNW>), dim3((unsigned)(groups * tn)), dim3(64 * G::NW), 0, st,
-                       (const unsigned short*)x, (const unsigned short*)w, (const unsigned short*)bias, (int)H, (int)W,
-                       (int)Cin, (int)N, (int)tn, mt, (unsigned short*)y, eps, (const unsigned short*)nw,
-                       (const unsigned short*)nb, (const unsigned short*)res);
+// k_conv3x3_halo over a halo_ok shape.  epi: 0 plain, 1 SiLU, 2 RMSNorm + residual; Epis: the ones the caller has.
+template <class Epis>
+static void launch_halo(Epis, int epi, const ConvArgs& a, hipStream_t st) {
+    dispatch_int(epi, Epis{}, [&](auto E) {
+        dispatch_int(a.N == 128 ? 4 : 2, std::integer_sequence<int, 4, 2>{}, [&](auto WM) {
+            constexpr int EPI = decltype(E)::value, WMW = decltype(WM)::value;
+            using G = HC<WMW>;
+            const int64_t tiles = a.B * (a.H / 16) * (a.W / G::TWD), tn = a.N / G::BN;
+            hipLaunchKernelGGL((k_conv3x3_halo<int(EPI == 1), EPI == 2, WMW, 8 / WMW>), dim3((unsigned)(tiles * tn)),
+                               dim3(64 * G::NW), 0, st, (const unsigned short*)a.x, (const unsigned short*)a.w,
+                               (const unsigned short*)a.bias, (int)a.H, (int)a.W, (int)a.Cin, (int)a.N, (int)tn,
+                               (unsigned short*)a.y, a.eps, (const unsigned short*)a.nw, (const unsigned short*)a.nb,
+                               (const unsigned short*)a.res);
+        });
+    });
 }
 
-template <int ACT, bool NORM, int WMW, int WNW, bool PAD>
-static void launch_halo_t(const void* x, const void* w, const void* bias, int64_t B, int64_t H, int64_t W, int64_t Cin,
-                          int64_t N, void* y, float eps, const void* nw, const void* nb, const void* res,
-                          hipStream_t st) {
-    using G = HC<WMW, WNW, PAD>;
-    const int64_t tiles = B * (H / 16) * (W / G::TWD), tn = N / G::BN;
-    hipLaunchKernelGGL((k_conv3x3_halo<ACT, NORM, WMW, WNW, PAD>), dim3((unsigned)(tiles * tn)), dim3(64 * G::NW), 0, st,
-                       (const unsigned short*)x, (const unsigned short*)w, (const unsigned short*)bias, (int)H, (int)W,
-                       (int)Cin, (int)N, (int)tn, (unsigned short*)y, eps, (const unsigned short*)nw,
-                       (const unsigned short*)nb, (const unsigned short*)res);
+// What every entry point checks for the tap-staged kernel (`fn` names the one called) over Mp GEMM rows of input
+// width W, and the launch geometry that follows.  tall: the 512 x 128 tile, else 256 x 256.
+struct Gemm8Geom {
+    int lcpt;  // log2 of the 64-channel slices per tap
+    int64_t Mp, tiles_n;
+    unsigned blocks;
+};
+static int gemm8_geom(const char* fn, int64_t Mp, int64_t W, int64_t Cin, int64_t N, int64_t ks, int64_t px, bool tall,
+                      Gemm8Geom* g) {
+    EGG_CHECK_ARG(Cin >= 64 && Cin <= 2048 && (Cin & (Cin - 1)) == 0, "%s: Cin=%lld must be a power of two in [64, 2048]",
+                  fn, (long long)Cin);
+    const int64_t BM = tall ? 512 : 256, BN = tall ? 128 : 256, K = ks * (px + ks - 1) * Cin;
+    EGG_CHECK_ARG(Mp < (1ll << 31) && (BM * (px + 1) + 2 * W + 8) * Cin * 2 < (1ll << 30) && N * K * 2 < (1ll << 31),
+                  "%s: sizes exceed the kernel's 32-bit offsets", fn);
+    const int64_t tiles_m = (Mp + BM - 1) / BM, tiles_n = (N + BN - 1) / BN;
+    EGG_CHECK_ARG(tiles_m * tiles_n < (1ll << 31), "%s: grid too large", fn);
+    int lcpt = 0;
+    while ((64ll << lcpt) < Cin) ++lcpt;
+    *g = Gemm8Geom{lcpt, Mp, tiles_n, (unsigned)(tiles_m * tiles_n)};
+    return EGGROLL_OK;
 }
 
-template <int ACT, bool NORM>
-static void launch_halo(int v, const void* x, const void* w, const void* bias, int64_t B, int64_t H, int64_t W,
-                        int64_t Cin, int64_t N, void* y, float eps, const void* nw, const void* nb, const void* res,
-                        hipStream_t st) {
-    if (v == 4) {
-        if (N == 128) launch_halo_mt_t<ACT, NORM, 4, 2>(x, w, bias, B, H, W, Cin, N, y, eps, nw, nb, res, st);
-        else launch_halo_mt_t<ACT, NORM, 2, 4>(x, w, bias, B, H, W, Cin, N, y, eps, nw, nb, res, st);
-        return;
-    }
-    if (v == 3 && N == 128) launch_halo_t<ACT, NORM, 4, 2, false>(x, w, bias, B, H, W, Cin, N, y, eps, nw, nb, res, st);
-    else if (v == 3) launch_halo_t<ACT, NORM, 2, 4, false>(x, w, bias, B, H, W, Cin, N, y, eps, nw, nb, res, st);
-    else if (N == 128) launch_halo_t<ACT, NORM, 4, 2, true>(x, w, bias, B, H, W, Cin, N, y, eps, nw, nb, res, st);
-    else launch_halo_t<ACT, NORM, 2, 4, true>(x, w, bias, B, H, W, Cin, N, y, eps, nw, nb, res, st);
+// A k_conv3x3_gemm8 instance as one integer for dispatch_int: the decimal digits PX ACT NORM KS WMW SP REP
+// (SP 0 with REP 2 is the template's default, the forms without the sub-pixel epilogue).
+constexpr int gemm8_id(int px, int act, bool norm, int ks, int wmw, int sp = 0, int rep = 2) {
+    return (((((px * 10 + act) * 10 + norm) * 10 + ks) * 10 + wmw) * 10 + sp) * 10 + rep;
+}
+// ks 2; the 512 x 128 tile; 256 x 256 at px 1; 256 x 256 at px 2 — each plain and SiLU
+using ConvIds = std::integer_sequence<int, gemm8_id(1, 0, false, 2, 2), gemm8_id(1, 1, false, 2, 2),
+                                      gemm8_id(1, 0, false, 3, 4), gemm8_id(1, 1, false, 3, 4),
+                                      gemm8_id(1, 0, false, 3, 2), gemm8_id(1, 1, false, 3, 2),
+                                      gemm8_id(2, 0, false, 3, 2), gemm8_id(2, 1, false, 3, 2)>;
+using NormIds = std::integer_sequence<int, gemm8_id(1, 0, true, 3, 4), gemm8_id(1, 0, true, 3, 2),
+                                      gemm8_id(2, 0, true, 3, 2)>;
+// bf16 (SP 1) and fp32 (SP 2) shortcut source at REP 1, 2, 4
+using SubpixIds = std::integer_sequence<int, gemm8_id(1, 0, false, 2, 2, 1, 1), gemm8_id(1, 0, false, 2, 2, 1, 2),
+                                        gemm8_id(1, 0, false, 2, 2, 1, 4), gemm8_id(1, 0, false, 2, 2, 2, 1),
+                                        gemm8_id(1, 0, false, 2, 2, 2, 2), gemm8_id(1, 0, false, 2, 2, 2, 4)>;
+
+template <class Ids>
+static void launch_gemm8(Ids, int id, const ConvArgs& a, const Gemm8Geom& g, const SubpixArgs& spa, hipStream_t st) {
+    dispatch_int(id, Ids{}, [&](auto ID) {
+        constexpr int V = decltype(ID)::value;
+        hipLaunchKernelGGL((k_conv3x3_gemm8<V / 1000000, V / 100000 % 10, V / 10000 % 10 != 0, V / 1000 % 10,
+                                            V / 100 % 10, V / 10 % 10, V % 10>),
+                           dim3(g.blocks), dim3(512), 0, st, (const unsigned short*)a.x, (const unsigned short*)a.w,
+                           (const unsigned short*)a.bias, (int)a.H, (int)a.W, (int)a.Cin, g.lcpt, (int)g.Mp, (int)a.N,
+                           (int)g.tiles_n, (unsigned short*)a.y, a.eps, (const unsigned short*)a.nw,
+                           (const unsigned short*)a.nb, (const unsigned short*)a.res, spa);
+    });
 }
 
 extern "C" {
@@ -1117,56 +860,25 @@ int eggroll_conv_nhwc(const void* x, const void* w_packed, const void* bias, int
 int eggroll_conv_nhwc_sel(const void* x, const void* w_packed, const void* bias, int64_t B, int64_t H, int64_t W,
                           int64_t Cin, int64_t N, int32_t ks, int32_t px, int32_t act, void* y, int32_t kernel,
                           void* stream) {
-    EGG_CHECK_ARG(kernel >= 0 && kernel <= 4, "conv_nhwc: kernel must be 0 (auto), 1 (tap-staged), 2, 3 or 4 (halo)");
     EGG_CHECK_ARG(ks == 2 || ks == 3, "conv_nhwc: ks must be 2 or 3 (got %d)", ks);
     EGG_CHECK_ARG(px == 1 || px == 2, "conv_nhwc: px must be 1 or 2 (got %d)", px);
     EGG_CHECK_ARG(ks == 3 || px == 1, "conv_nhwc: px 2 needs ks 3");
     EGG_CHECK_ARG(act == 0 || act == 2, "conv_nhwc: act must be 0 (none) or 2 (silu) (got %d)", act);
     const int64_t Ho = H + 3 - ks, Wo = W + 3 - ks;
     EGG_CHECK_ARG(B > 0 && H > 0 && W > 0 && Wo % px == 0, "conv_nhwc: bad B/H/W (output width %% px == 0 required)");
-    EGG_CHECK_ARG(Cin >= 64 && Cin <= 2048 && (Cin & (Cin - 1)) == 0,
-                  "conv_nhwc: Cin=%lld must be a power of two in [64, 2048]", (long long)Cin);
     EGG_CHECK_ARG(N >= 64 && N % 64 == 0 && N <= 8192, "conv_nhwc: N=%lld must be a multiple of 64 (<= 8192)",
                   (long long)N);
-    const int64_t Mp = B * Ho * (Wo / px);
-    const int64_t K = ks * (px + ks - 1) * Cin;
     // Cout = 128 at px 1 (3x3): the 512 x 128 tile (no zero MACs); everything else 256 x 256
     const bool tall = ks == 3 && px == 1 && N == 128;
-    const int64_t BM = tall ? 512 : 256, BN = tall ? 128 : 256;
-    EGG_CHECK_ARG(Mp < (1ll << 31) && (BM * (px + 1) + 2 * W + 8) * Cin * 2 < (1ll << 30) && N * K * 2 < (1ll << 31),
-                  "conv_nhwc: sizes exceed the kernel's 32-bit offsets");
+    Gemm8Geom g;
+    if (int rc = gemm8_geom("conv_nhwc", B * Ho * (Wo / px), W, Cin, N, ks, px, tall, &g)) return rc;
     EGG_CHECK_ARG(x && w_packed && y, "conv_nhwc: NULL pointer");
-    const int64_t tiles_m = (Mp + BM - 1) / BM, tiles_n = (N + BN - 1) / BN;
-    EGG_CHECK_ARG(tiles_m * tiles_n < (1ll << 31), "conv_nhwc: grid too large");
-    const int hv = kernel == 0 ? 2 : kernel;
-    const bool hok = halo_ok(hv, ks, px, H, W, Cin, N);
-    EGG_CHECK_ARG(kernel < 2 || hok, "conv_nhwc: halo kernel %d needs ks 3, px 1, H %% 16 == 0 and W, N multiples of "
-                  "the tile (see include/eggroll.h)", kernel);
-    hipStream_t st = as_stream(stream);
-    if (hok && kernel != 1) {
-        if (act == 0) launch_halo<0, false>(hv, x, w_packed, bias, B, H, W, Cin, N, y, 0.0f, nullptr, nullptr, nullptr, st);
-        else launch_halo<1, false>(hv, x, w_packed, bias, B, H, W, Cin, N, y, 0.0f, nullptr, nullptr, nullptr, st);
-        EGG_CHECK_LAUNCH("conv_nhwc");
-        return EGGROLL_OK;
-    }
-    int lcpt = 0;
-    while ((64ll << lcpt) < Cin) ++lcpt;
-    const dim3 grid((unsigned)(tiles_m * tiles_n));
-#define EGG_CONV(PX_, ACT_, KS_, WMW_)                                                                          \
-    hipLaunchKernelGGL((k_conv3x3_gemm8<PX_, ACT_, false, KS_, WMW_>), grid, dim3(512), 0, st,                  \
-                       (const unsigned short*)x, (const unsigned short*)w_packed, (const unsigned short*)bias, \
-                       (int)H, (int)W, (int)Cin, lcpt, (int)Mp, (int)N, (int)tiles_n, (unsigned short*)y, 0.0f,   \
-                       nullptr, nullptr, nullptr)
-    if (ks == 2) {
-        if (act == 0) EGG_CONV(1, 0, 2, 2);
-        else EGG_CONV(1, 1, 2, 2);
-    } else if (tall && act == 0) EGG_CONV(1, 0, 3, 4);
-    else if (tall) EGG_CONV(1, 1, 3, 4);
-    else if (px == 1 && act == 0) EGG_CONV(1, 0, 3, 2);
-    else if (px == 1) EGG_CONV(1, 1, 3, 2);
-    else if (act == 0) EGG_CONV(2, 0, 3, 2);
-    else EGG_CONV(2, 1, 3, 2);
-#undef EGG_CONV
+    bool halo;
+    if (int rc = conv_kernel_sel("conv_nhwc", kernel, ks, px, H, W, Cin, N, &halo)) return rc;
+    const ConvArgs a{x, w_packed, bias, B, H, W, Cin, N, y};
+    const int silu = act != 0;
+    if (halo) launch_halo(std::integer_sequence<int, 0, 1>{}, silu, a, as_stream(stream));
+    else launch_gemm8(ConvIds{}, gemm8_id(px, silu, false, ks, tall ? 4 : 2), a, g, SubpixArgs{}, as_stream(stream));
     EGG_CHECK_LAUNCH("conv_nhwc");
     return EGGROLL_OK;
 }
@@ -1175,8 +887,8 @@ int eggroll_conv2x2_subpixel_nhwc(const void* x, const void* w_packed, const voi
                                   int32_t src_f32, int64_t B, int64_t H, int64_t W, int64_t Cin, int64_t Cout,
                                   void* out, void* shadow, void* stream) {
     EGG_CHECK_ARG(B > 0 && H > 0 && W > 0, "conv2x2_subpixel: bad B/H/W");
-    EGG_CHECK_ARG(Cin >= 64 && Cin <= 2048 && (Cin & (Cin - 1)) == 0,
-                  "conv2x2_subpixel: Cin=%lld must be a power of two in [64, 2048]", (long long)Cin);
+    Gemm8Geom g;  // the ks-2 phase conv over the (H+1) x (W+1) grid, N = 4 * Cout
+    if (int rc = gemm8_geom("conv2x2_subpixel", B * (H + 1) * (W + 1), W, Cin, 4 * Cout, 2, 1, false, &g)) return rc;
     EGG_CHECK_ARG(Cout >= 64 && Cout % 64 == 0 && 4 * Cout <= 8192 && (4 * Cout) % Cin == 0,
                   "conv2x2_subpixel: Cout=%lld must be a multiple of 64 with 4*Cout a multiple of Cin", (long long)Cout);
     const int64_t rep = 4 * Cout / Cin;
@@ -1184,36 +896,15 @@ int eggroll_conv2x2_subpixel_nhwc(const void* x, const void* w_packed, const voi
                   (long long)rep);
     EGG_CHECK_ARG(src_f32 == 0 || src_f32 == 1, "conv2x2_subpixel: src_f32 must be 0 or 1");
     EGG_CHECK_ARG(src_f32 || !shadow, "conv2x2_subpixel: shadow needs the fp32 form");
-    const int64_t Mp = B * (H + 1) * (W + 1), N = 4 * Cout, K = 4 * Cin;
-    EGG_CHECK_ARG(Mp < (1ll << 31) && (256 * 2 + 2 * W + 8) * Cin * 2 < (1ll << 30) && N * K * 2 < (1ll << 31) &&
-                      B * 4 * H * W * Cout < (1ll << 31),
-                  "conv2x2_subpixel: sizes exceed the kernel's offsets");
+    EGG_CHECK_ARG(B * 4 * H * W * Cout < (1ll << 31), "conv2x2_subpixel: sizes exceed the kernel's 32-bit offsets");
     EGG_CHECK_ARG(x && w_packed && src && out, "conv2x2_subpixel: NULL pointer");
     EGG_CHECK_ARG(((uintptr_t)x & 15) == 0 && ((uintptr_t)src & 15) == 0 && ((uintptr_t)out & 15) == 0 &&
                       ((uintptr_t)shadow & 15) == 0 && ((uintptr_t)bias & 15) == 0,
                   "conv2x2_subpixel: pointers must be 16-byte aligned");
-    const int64_t tiles_m = (Mp + 255) / 256, tiles_n = N / 256 + (N % 256 != 0);
-    EGG_CHECK_ARG(tiles_m * tiles_n < (1ll << 31), "conv2x2_subpixel: grid too large");
-    int lcpt = 0;
-    while ((64ll << lcpt) < Cin) ++lcpt;
     const SubpixArgs spa{(const unsigned short*)bias, src, out, (unsigned short*)shadow, (int)H, (int)W, (int)Cin,
                          (int)Cout};
-    hipStream_t st = as_stream(stream);
-    const dim3 grid((unsigned)(tiles_m * tiles_n));
-#define EGG_SPX(SP_, REP_)                                                                                      \
-    hipLaunchKernelGGL((k_conv3x3_gemm8<1, 0, false, 2, 2, SP_, REP_>), grid, dim3(512), 0, st,                 \
-                       (const unsigned short*)x, (const unsigned short*)w_packed, nullptr, (int)H, (int)W, (int)Cin, \
-                       lcpt, (int)Mp, (int)N, (int)tiles_n, nullptr, 0.0f, nullptr, nullptr, nullptr, spa)
-    if (src_f32) {
-        if (rep == 1) EGG_SPX(2, 1);
-        else if (rep == 2) EGG_SPX(2, 2);
-        else EGG_SPX(2, 4);
-    } else {
-        if (rep == 1) EGG_SPX(1, 1);
-        else if (rep == 2) EGG_SPX(1, 2);
-        else EGG_SPX(1, 4);
-    }
-#undef EGG_SPX
+    const ConvArgs a{x, w_packed, nullptr, B, H, W, Cin, 4 * Cout, nullptr};  // bias and output: the epilogue's (spa)
+    launch_gemm8(SubpixIds{}, gemm8_id(1, 0, false, 2, 2, src_f32 ? 2 : 1, (int)rep), a, g, spa, as_stream(stream));
     EGG_CHECK_LAUNCH("conv2x2_subpixel_nhwc");
     return EGGROLL_OK;
 }
@@ -1234,46 +925,24 @@ int eggroll_conv3x3_rmsnorm_nhwc(const void* x, const void* w_packed, const void
 int eggroll_conv3x3_rmsnorm_nhwc_sel(const void* x, const void* w_packed, const void* bias, int64_t B, int64_t H,
                                      int64_t W, int64_t Cin, int64_t N, int32_t px, float eps, const void* norm_w,
                                      const void* norm_b, const void* res, void* y, int32_t kernel, void* stream) {
-    EGG_CHECK_ARG(kernel >= 0 && kernel <= 4,
-                  "conv3x3_rmsnorm_nhwc: kernel must be 0 (auto), 1 (tap-staged), 2, 3 or 4 (halo)");
     EGG_CHECK_ARG(px == 1 || px == 2, "conv3x3_rmsnorm_nhwc: px must be 1 or 2 (got %d)", px);
     EGG_CHECK_ARG(N == 256 || (N == 128 && px == 1),
                   "conv3x3_rmsnorm_nhwc: N = px * Cout must be 256, or 128 at px 1 (got %lld, px %d)", (long long)N, px);
     const bool tall = N == 128;  // 512 x 128 tile
     EGG_CHECK_ARG(B > 0 && H > 0 && W > 0 && W % px == 0, "conv3x3_rmsnorm_nhwc: bad B/H/W (W %% px == 0 required)");
-    EGG_CHECK_ARG(Cin >= 64 && Cin <= 2048 && (Cin & (Cin - 1)) == 0,
-                  "conv3x3_rmsnorm_nhwc: Cin=%lld must be a power of two in [64, 2048]", (long long)Cin);
-    const int64_t Mp = B * H * (W / px);
-    const int64_t BM = tall ? 512 : 256;
-    EGG_CHECK_ARG(Mp < (1ll << 31) && (BM * (px + 1) + 2 * W + 8) * Cin * 2 < (1ll << 30),
-                  "conv3x3_rmsnorm_nhwc: sizes exceed the kernel's 32-bit offsets");
+    Gemm8Geom g;
+    if (int rc = gemm8_geom("conv3x3_rmsnorm_nhwc", B * H * (W / px), W, Cin, N, 3, px, tall, &g)) return rc;
     EGG_CHECK_ARG(x && w_packed && y && norm_w && res, "conv3x3_rmsnorm_nhwc: NULL pointer");
     EGG_CHECK_ARG(((uintptr_t)res & 7) == 0, "conv3x3_rmsnorm_nhwc: res must be 8-byte aligned");
     EGG_CHECK_ARG(res != y && x != y, "conv3x3_rmsnorm_nhwc: y may not alias x or res");
-    const int hv = kernel == 0 ? 2 : kernel;
-    const bool hok = halo_ok(hv, 3, px, H, W, Cin, N);
-    EGG_CHECK_ARG(kernel < 2 || hok, "conv3x3_rmsnorm_nhwc: halo kernel %d needs px 1, H %% 16 == 0 and W a multiple "
-                  "of the tile width (see include/eggroll.h)", kernel);
-    hipStream_t st = as_stream(stream);
-    if (hok && kernel != 1) {
-        launch_halo<0, true>(hv, x, w_packed, bias, B, H, W, Cin, N, y, eps, norm_w, norm_b, res, st);
-        EGG_CHECK_LAUNCH("conv3x3_rmsnorm_nhwc");
-        return EGGROLL_OK;
-    }
-    int lcpt = 0;
-    while ((64ll << lcpt) < Cin) ++lcpt;
-    const dim3 grid((unsigned)((Mp + BM - 1) / BM));
-#define EGG_CONVN(PX_, WMW_)                                                                                    \
-    hipLaunchKernelGGL((k_conv3x3_gemm8<PX_, 0, true, 3, WMW_>), grid, dim3(512), 0, st, (const unsigned short*)x, \
-                       (const unsigned short*)w_packed, (const unsigned short*)bias, (int)H, (int)W, (int)Cin, lcpt, \
-                       (int)Mp, (int)N, 1, (unsigned short*)y, eps, (const unsigned short*)norm_w,              \
-                       (const unsigned short*)norm_b, (const unsigned short*)res)
-    if (tall) EGG_CONVN(1, 4);
-    else if (px == 1) EGG_CONVN(1, 2);
-    else EGG_CONVN(2, 2);
-#undef EGG_CONVN
+    bool halo;
+    if (int rc = conv_kernel_sel("conv3x3_rmsnorm_nhwc", kernel, 3, px, H, W, Cin, N, &halo)) return rc;
+    const ConvArgs a{x, w_packed, bias, B, H, W, Cin, N, y, eps, norm_w, norm_b, res};
+    if (halo) launch_halo(std::integer_sequence<int, 2>{}, 2, a, as_stream(stream));
+    else launch_gemm8(NormIds{}, gemm8_id(px, 0, true, 3, tall ? 4 : 2), a, g, SubpixArgs{}, as_stream(stream));
     EGG_CHECK_LAUNCH("conv3x3_rmsnorm_nhwc");
     return EGGROLL_OK;
 }
 
 }  // extern "C"
+

@@ -1106,26 +1106,7 @@ def conv3x3_nhwc(x: torch.Tensor, w_packed: torch.Tensor, bias: Optional[torch.T
                  act: Optional[str] = None, out: Optional[torch.Tensor] = None, kernel: int = 0) -> torch.Tensor:
     """3x3 conv (stride 1, pad 1) of x [B,H,W,Cin] NHWC bf16 with a pack_conv3x3_weight operand;
     bias [px*Cout] (the conv bias repeated px times) or None; act None / 'silu'.  -> [B,H,W,Cout]."""
-    _dev(x, "conv3x3(x)", torch.bfloat16)
-    _dev(w_packed, "conv3x3(w)", torch.bfloat16)
-    x = x.contiguous()
-    B, H, W, Cin = x.shape
-    N = w_packed.shape[0]
-    if w_packed.shape[1] != 3 * (px + 2) * Cin or N % px:
-        raise ValueError(f"conv3x3: packed weight {tuple(w_packed.shape)} does not match Cin={Cin}, px={px}")
-    if bias is not None:
-        _dev(bias, "conv3x3(bias)", torch.bfloat16)
-        if bias.numel() != N:
-            raise ValueError(f"conv3x3: bias has {bias.numel()} entries, need {N}")
-    Cout = N // px
-    if out is None:
-        out = torch.empty((B, H, W, Cout), dtype=torch.bfloat16, device=x.device)
-    e0 = OpTimer.begin()
-    _lib.call("eggroll_conv_nhwc_sel", x.data_ptr(), w_packed.data_ptr(), _p(bias), B, H, W, Cin, N, 3, px,
-              ACT[act], out.data_ptr(), int(kernel), _stream(x.device))
-    OpTimer.end(e0, "conv3x3", 2.0 * (x.numel() + out.numel()), f"{tuple(x.shape)}->{Cout} px{px}",
-                flops=2.0 * B * H * W * Cout * 9 * Cin)
-    return out
+    return conv_nhwc(x, w_packed, bias, 3, px, act, out, kernel)
 
 
 def conv3x3_rmsnorm_nhwc(x: torch.Tensor, w_packed: torch.Tensor, bias: Optional[torch.Tensor], px: int, eps: float,

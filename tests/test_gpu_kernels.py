@@ -903,18 +903,16 @@ def test_conv3x3_rmsnorm_nhwc_vs_torch(dev, B, H, W, Cin, px, Cout):
     (2, 16, 48, 64, 256, False, "silu"),     # Cin 64 -> 256
     (1, 16, 32, 512, 512, True, None),       # N = 512: two column tiles share each pixel tile
 ])
-@pytest.mark.parametrize("kern", [2, 3])
-def test_conv3x3_halo_vs_torch(dev, B, H, W, Cin, Cout, bias, act, kern):
-    """Halo-staged conv (512x128 / 256x256 tiles, one 8-wave workgroup per CU; kernel 2: halo rows padded
-    to 8 pixels, kernel 3: the unpadded layout) vs torch fp32 on the same bf16 inputs (same bound as the
-    tap-staged kernel), vs the tap-staged kernel (1) — both round an fp32 sum once — and kernel 2 == 3
-    bitwise (same MFMA sequence, only the LDS layout differs)."""
+def test_conv3x3_halo_vs_torch(dev, B, H, W, Cin, Cout, bias, act):
+    """Halo-staged conv (kernel 2: 512x128 / 256x256 tiles, one 8-wave workgroup per CU, halo rows padded
+    to 8 pixels) vs torch fp32 on the same bf16 inputs (same bound as the tap-staged kernel) and vs the
+    tap-staged kernel (1) — both round an fp32 sum once."""
     g = torch.Generator().manual_seed(B * 100 + H + Cin)
     x = torch.randn(B, H, W, Cin, generator=g).to(dev, torch.bfloat16)
     w = (torch.randn(Cout, Cin, 3, 3, generator=g) / math.sqrt(9 * Cin)).to(dev, torch.bfloat16)
     b = (torch.randn(Cout, generator=g) * 0.5).to(dev, torch.bfloat16) if bias else None
     wp = K.pack_conv3x3_weight(w, 1)
-    y = K.conv3x3_nhwc(x, wp, b, 1, act, kernel=kern)
+    y = K.conv3x3_nhwc(x, wp, b, 1, act, kernel=2)
     y1 = K.conv3x3_nhwc(x, wp, b, 1, act, kernel=1)
     ref = torch.nn.functional.conv2d(x.permute(0, 3, 1, 2).float(), w.float(), b.float() if bias else None, padding=1)
     if act == "silu":
@@ -925,12 +923,11 @@ def test_conv3x3_halo_vs_torch(dev, B, H, W, Cin, Cout, bias, act, kern):
     assert bool((err <= tol).all()), f"max err {err.max().item():.3e} (ref max {ref.abs().max().item():.3e})"
     d = (y.float() - y1.float()).abs()
     assert bool((d <= 2.0 ** -7 * ref.abs() + 1e-3 * ref.abs().max()).all())
-    assert torch.equal(y, K.conv3x3_nhwc(x, wp, b, 1, act, kernel=5 - kern))
 
 
 @pytest.mark.parametrize("B,H,W,Cin,Cout,kern", [(2, 16, 32, 128, 128, 2), (1, 32, 64, 64, 128, 2),
-                                                  (1, 32, 32, 256, 256, 2), (2, 16, 32, 128, 128, 3),
-                                                  (1, 32, 64, 256, 128, 3), (1, 16, 48, 512, 256, 3)])
+                                                  (1, 32, 32, 256, 256, 2), (1, 32, 64, 256, 128, 2),
+                                                  (1, 16, 48, 512, 256, 2)])
 def test_conv3x3_rmsnorm_halo_vs_torch(dev, B, H, W, Cin, Cout, kern):
     """conv -> RMSNorm -> + res on the halo kernel (2-D tile rows mapped to NHWC pixels)."""
     g = torch.Generator().manual_seed(3 + W)
@@ -952,42 +949,30 @@ def test_conv3x3_rmsnorm_halo_vs_torch(dev, B, H, W, Cin, Cout, kern):
     assert bool((err <= tol).all()), f"max err {err.max().item():.3e}"
 
 
-@pytest.mark.parametrize("B,H,W,Cin,Cout", [
-    (2, 64, 32, 128, 128),    # 4 row bands: 4 tiles per workgroup (512 x 128 tile)
-    (1, 32, 64, 64, 128),     # 2 bands: 2 tiles per workgroup, Cin 64 (two slices: no middle slice)
-    (1, 48, 32, 256, 128),    # 3 bands: 1 tile per workgroup (the chunked epilogue alone)
-    (1, 64, 32, 256, 256),    # 256 x 256 tile, 4 tiles per workgroup
-    (2, 32, 16, 512, 512),    # N = 512: two column tiles per tile stack
-])
-def test_conv3x3_halo_multitile_bitexact(dev, B, H, W, Cin, Cout):
-    """Kernel 4 (one workgroup streams several vertically stacked tiles: the next tile's halo and first
-    weights in flight during the current tile's last slice, C tiles through a dedicated staging region)
-    runs the same MFMA sequence per tile as kernel 2: bit-identical outputs, plain / SiLU + bias /
-    RMSNorm + residual."""
-    g = torch.Generator().manual_seed(H * 7 + Cin)
-    x = torch.randn(B, H, W, Cin, generator=g).to(dev, torch.bfloat16)
-    w = (torch.randn(Cout, Cin, 3, 3, generator=g) / math.sqrt(9 * Cin)).to(dev, torch.bfloat16)
-    b = (torch.randn(Cout, generator=g) * 0.5).to(dev, torch.bfloat16)
-    wp = K.pack_conv3x3_weight(w, 1)
-    for bias, act in [(None, None), (b, "silu")]:
-        y2 = K.conv3x3_nhwc(x, wp, bias, 1, act, kernel=2)
-        y4 = K.conv3x3_nhwc(x, wp, bias, 1, act, kernel=4)
-        assert torch.equal(y2, y4), (bias is None, act)
-    if Cout in (128, 256):
-        nw = (1 + 0.2 * torch.randn(Cout, generator=g)).to(dev, torch.bfloat16)
-        nb = (0.2 * torch.randn(Cout, generator=g)).to(dev, torch.bfloat16)
-        res = torch.randn(B, H, W, Cout, generator=g).to(dev, torch.bfloat16)
-        z2 = K.conv3x3_rmsnorm_nhwc(x, wp, b, 1, 1e-5, nw, nb, res, kernel=2)
-        z4 = K.conv3x3_rmsnorm_nhwc(x, wp, b, 1, 1e-5, nw, nb, res, kernel=4)
-        assert torch.equal(z2, z4)
-
-
 def test_conv3x3_halo_rejects_ragged(dev):
     x = torch.zeros(1, 8, 8, 64, device=dev, dtype=torch.bfloat16)   # H % 16 != 0
     w = K.pack_conv3x3_weight(torch.zeros(128, 64, 3, 3, device=dev, dtype=torch.bfloat16), 1)
     with pytest.raises(RuntimeError):
         K.conv3x3_nhwc(x, w, None, 1, kernel=2)
     K.conv3x3_nhwc(x, w, None, 1, kernel=0)   # auto falls back to the tap-staged kernel
+
+
+def test_conv3x3_rejects_removed_halo_variants(dev):
+    """Selectors 3 and 4 (the unpadded and the multi-tile halo variants, removed) are refused like any other
+    bad value, on a shape the halo kernel accepts, and a refused call launches nothing: the output buffer
+    keeps its sentinel."""
+    x = torch.zeros(1, 16, 32, 64, device=dev, dtype=torch.bfloat16)
+    w = K.pack_conv3x3_weight(torch.zeros(128, 64, 3, 3, device=dev, dtype=torch.bfloat16), 1)
+    nw = torch.ones(128, device=dev, dtype=torch.bfloat16)
+    res = torch.zeros(1, 16, 32, 128, device=dev, dtype=torch.bfloat16)
+    buf = torch.full((1, 16, 32, 128), 7.0, device=dev, dtype=torch.bfloat16)
+    for k in (3, 4):
+        with pytest.raises(RuntimeError):
+            K.conv3x3_nhwc(x, w, None, 1, out=buf, kernel=k)
+        with pytest.raises(RuntimeError):
+            K.conv3x3_rmsnorm_nhwc(x, w, None, 1, 1e-5, nw, None, res, kernel=k)
+    torch.cuda.synchronize()
+    assert bool((buf == 7.0).all())
 
 
 @pytest.mark.parametrize("B,H,W,Cin,N", [(2, 6, 5, 64, 128), (1, 16, 16, 128, 512), (3, 9, 4, 256, 64)])

@@ -1,8 +1,6 @@
-"""Where a multi-tile halo conv workgroup's time goes (kernel 4) vs the one-tile kernel (2): s_memtime
-stamps from a -DEGG_STAMPS build (tools/_stamps/libeggroll_stamps.so, `python tools/halo_stamp_probe.py
-build`; never loaded by the package).  Kernel 2 stamps: 0 start, 1 prologue landed, 2 main loop done,
-3 ring drained, 4 epilogue math, 5 stores drained.  Kernel 4: 0 start, 1 first tile's data landed,
-2 tile 0's main loop done, 3 tile 0's epilogue done, 5 all tiles done -> the later tiles' average.
+"""Where a halo conv workgroup's time goes (kernel 2): s_memtime stamps from a -DEGG_STAMPS build
+(tools/_ab/libeggroll_stamps.so, `python tools/halo_stamp_probe.py build`; never loaded by the package).
+Stamps: 0 start, 1 prologue landed, 2 main loop done, 3 ring drained, 4 epilogue math, 5 stores drained.
 usage: python tools/halo_stamp_probe.py [build]"""
 import ctypes
 import json
@@ -44,34 +42,27 @@ def main():
         w = (torch.randn(C, C, 3, 3, device=dev) / (9 * C) ** 0.5).to(torch.bfloat16)
         wp = K.pack_conv3x3_weight(w, 1)
         y = torch.empty_like(x)
-        tiles = (8 * hw * hw // 512) if C == 128 else (8 * hw * hw // 256) * (C // 256)
-        for kern in (2, 4):
-            nblk = tiles if kern == 2 else tiles // 4
-            for _ in range(3):
-                assert lib.eggroll_conv_nhwc_sel(vp(x.data_ptr()), vp(wp.data_ptr()), None, i64(8), i64(hw), i64(hw),
-                                                 i64(C), i64(C), i32(3), i32(1), i32(0), vp(y.data_ptr()), i32(kern),
-                                                 st) == 0
-            torch.cuda.synchronize()
-            buf = np.zeros(nblk * 8, dtype=np.uint64)
-            assert lib.eggroll_debug_conv_stamps(buf.ctypes.data, buf.size) == 0
-            s = buf.reshape(nblk, 8).astype(np.int64)
-            clk = np.median((s[:, 5] - s[:, 0]) / np.maximum(s[:, 7] - s[:, 6], 1) * 100e6)
-            med = lambda v: int(np.median(v))  # noqa: E731
-            if kern == 2:
-                out = {"prologue": med(s[:, 1] - s[:, 0]), "main": med(s[:, 2] - s[:, 1]),
-                       "drain": med(s[:, 3] - s[:, 2]), "epilogue": med(s[:, 5] - s[:, 3]),
-                       "tile": med(s[:, 5] - s[:, 0])}
-            else:
-                out = {"tile0_prologue": med(s[:, 1] - s[:, 0]), "tile0_main": med(s[:, 2] - s[:, 1]),
-                       "tile0_epilogue": med(s[:, 3] - s[:, 2]), "later_tile_avg": med((s[:, 5] - s[:, 3]) / 3),
-                       "workgroup": med(s[:, 5] - s[:, 0])}
-            wall = float(s[:, 7].max() - s[:, 6].min()) * 10e-9
-            out.update({"kernel": kern, "shape": f"8x{hw}x{hw}x{C}", "clock_GHz": round(clk / 1e9, 3),
-                        "wall_us": round(wall * 1e6, 1),
-                        # cycles per workgroup a CU delivers (wall x clock x 256 CUs / workgroups): vs the
-                        # median workgroup duration, the time lost between workgroups
-                        "cu_cycles_per_workgroup": int(wall * clk * 256 / nblk)})
-            print(json.dumps(out), flush=True)
+        nblk = (8 * hw * hw // 512) if C == 128 else (8 * hw * hw // 256) * (C // 256)
+        for _ in range(3):
+            assert lib.eggroll_conv_nhwc_sel(vp(x.data_ptr()), vp(wp.data_ptr()), None, i64(8), i64(hw), i64(hw),
+                                             i64(C), i64(C), i32(3), i32(1), i32(0), vp(y.data_ptr()), i32(2),
+                                             st) == 0
+        torch.cuda.synchronize()
+        buf = np.zeros(nblk * 8, dtype=np.uint64)
+        assert lib.eggroll_debug_conv_stamps(buf.ctypes.data, buf.size) == 0
+        s = buf.reshape(nblk, 8).astype(np.int64)
+        clk = np.median((s[:, 5] - s[:, 0]) / np.maximum(s[:, 7] - s[:, 6], 1) * 100e6)
+        med = lambda v: int(np.median(v))  # noqa: E731
+        out = {"prologue": med(s[:, 1] - s[:, 0]), "main": med(s[:, 2] - s[:, 1]),
+               "drain": med(s[:, 3] - s[:, 2]), "epilogue": med(s[:, 5] - s[:, 3]),
+               "tile": med(s[:, 5] - s[:, 0])}
+        wall = float(s[:, 7].max() - s[:, 6].min()) * 10e-9
+        out.update({"shape": f"8x{hw}x{hw}x{C}", "clock_GHz": round(clk / 1e9, 3),
+                    "wall_us": round(wall * 1e6, 1),
+                    # cycles per workgroup a CU delivers (wall x clock x 256 CUs / workgroups): vs the
+                    # median workgroup duration, the time lost between workgroups
+                    "cu_cycles_per_workgroup": int(wall * clk * 256 / nblk)})
+        print(json.dumps(out), flush=True)
         del x, y
 
 

@@ -23,9 +23,9 @@ NOTES = {"vgpr": ".vgpr_count", "agpr": ".agpr_count", "sgpr": ".sgpr_count", "v
          "sgpr_spill": ".sgpr_spill_count", "private_segment": ".private_segment_fixed_size",
          "lds": ".group_segment_fixed_size"}
 
-# (pattern, replacement) pairs: old demangled kernel name -> its new name.  The attention kernels kept their names
-# when they moved to eggroll_attn.hip, so the table is empty.
-RENAMES = []
+# (pattern, replacement) pairs: old demangled kernel name -> its new name.  The halo conv lost its last template
+# argument (PAD; the padded form `true` is the one that stayed).
+RENAMES = [(re.compile(r"(k_conv3x3_halo<[^<>]*), true>"), r"\1>")]
 
 
 def demangle(names):

@@ -3,8 +3,8 @@ global library handle is swapped between bound builds, each op's outputs are com
 first build's, then timed interleaved (median of rounds, HIP events on the launch stream).  Ops: the
 epoch's row norms (Sana AdaLN on the fp32 stream with fp32 modulation, C = 2240; bf16 rows, C = 2240;
 DC-AE RMSNorm + bias + fp32 residual, C = 512 and 1024), resid_layernorm (CLIP towers), the Z-Image q/k
-norm + RoPE and the DC-AE decoder head; small_cases adds one small case per remaining entry point of the
-nhwc / norm / qk / linattn / image units and per branch of their host-side kernel choices.
+norm + RoPE, the DC-AE decoder head and the DC-AE convs; small_cases adds one small case per remaining entry
+point of the conv / nhwc / norm / qk / linattn / image units and per branch of their host-side kernel choices.
 usage: python tools/ops_lib_ab.py <libA.so> <libB.so> [...] [--only=SUBSTRING] [--once]"""
 import json
 import statistics
@@ -58,6 +58,12 @@ def cases(dev, g):
         nwc, nbc, resc = r(Cc, sc=0.5), r(Cc, sc=0.1), r(Bc, Hc, Hc, Cc)
         out[f"conv3x3_rmsnorm {Bc}x{Hc}^2x{Cc}"] = (lambda xc=xc, wpk=wpk, nwc=nwc, nbc=nbc, resc=resc:
             K.conv3x3_rmsnorm_nhwc(xc, wpk, None, 1, 1e-6, nwc, nbc, resc))
+    # DC-AE ResBlock conv1 (halo kernel): plain and bias + SiLU at the three product shapes
+    for Bc, Hc, Cc in ((8, 1024, 128), (8, 512, 256), (8, 256, 512)):
+        xc, wpk, bc = r(Bc, Hc, Hc, Cc, sc=0.5), r(Cc, 9 * Cc, sc=(9 * Cc) ** -0.5), r(Cc, sc=0.1)
+        out[f"conv3x3 {Bc}x{Hc}^2x{Cc}"] = lambda xc=xc, wpk=wpk: K.conv3x3_nhwc(xc, wpk, None, 1)
+        out[f"conv3x3 bias+silu {Bc}x{Hc}^2x{Cc}"] = (lambda xc=xc, wpk=wpk, bc=bc:
+            K.conv3x3_nhwc(xc, wpk, bc, 1, "silu"))
     # flash attention (head dim 128): Z-Image's joint sequence (4 images x 4096+512 tokens x 30 heads) and a
     # ragged one (a partial key block, Nq not a multiple of the query tile)
     for Bf, Nf, Hf in ((4, 4608, 30), (2, 1000, 8)):
@@ -173,6 +179,37 @@ def small_cases(dev, r):
                 o = K.subpixel_shortcut_f32(y4, xs.float(), bs, sh)
                 return torch.cat([o.flatten(), sh.float().flatten()])
             out[f"subpixel_shortcut_f32 {cin}->{cout}"] = sp32
+    # dense convs: every kernel instance the conv dispatch can launch.  Ragged shapes run the tap-staged kernel
+    # under kernel 0 (ks 2; the 512 x 128 tile; 256 x 256 at px 1 and px 2); H = 16 with W = 32 (N = 128) or
+    # W = 16 (N = 256) runs the halo kernel, and the tap-staged RMSNorm forms once more there under kernel 1
+    for tag, shp, cout, ks, px, kerns in (("ks2", (1, 7, 10, 128), 128, 2, 1, (0,)),
+                                          ("tall", (1, 7, 10, 128), 128, 3, 1, (0,)),
+                                          ("px1", (1, 9, 12, 256), 256, 3, 1, (0,)),
+                                          ("px2", (1, 7, 10, 128), 128, 3, 2, (0,)),
+                                          ("halo tall", (1, 16, 32, 128), 128, 3, 1, (0, 1)),
+                                          ("halo 256", (1, 16, 16, 256), 256, 3, 1, (0, 1))):
+        xc = r(*shp, sc=0.5)
+        wpk = K.pack_conv3x3_weight(r(cout, shp[3], ks, ks, sc=(ks * ks * shp[3]) ** -0.5), px)
+        bc, nwc, nbc = r(cout, sc=0.1).repeat(px), r(cout, sc=0.5), r(cout, sc=0.1)
+        resc = r(*shp[:3], cout)
+        out[f"conv {tag} {shp}"] = lambda xc=xc, wpk=wpk, ks=ks, px=px: K.conv_nhwc(xc, wpk, None, ks, px)
+        out[f"conv {tag} bias+silu {shp}"] = (lambda xc=xc, wpk=wpk, bc=bc, ks=ks, px=px:
+            K.conv_nhwc(xc, wpk, bc, ks, px, "silu"))
+        for kern in kerns if ks == 3 else ():
+            out[f"conv_rmsnorm {tag} kernel {kern} {shp}"] = (
+                lambda xc=xc, wpk=wpk, bc=bc, px=px, nwc=nwc, nbc=nbc, resc=resc, kern=kern:
+                K.conv3x3_rmsnorm_nhwc(xc, wpk, bc, px, 1e-5, nwc, nbc, resc, kernel=kern))
+    # conv2x2_subpixel: REP = 4 Cout / Cin of 1, 2, 4 with a bf16 and an fp32 shortcut source
+    for cin in (256, 128, 64):
+        xs, bs = r(2, 5, 7, cin, sc=0.5), r(64, sc=0.1)
+        w4p = K.pack_conv3x3_weight(r(256, cin, 2, 2, sc=(4 * cin) ** -0.5), 1)
+        out[f"conv2x2_subpixel {cin}->64"] = lambda xs=xs, w4p=w4p, bs=bs: K.conv2x2_subpixel(xs, w4p, xs, bias=bs)
+
+        def spx32(xs=xs, w4p=w4p, bs=bs, src=r(2, 5, 7, cin, dt=torch.float32)):
+            sh = torch.empty(2, 10, 14, 64, device=dev, dtype=torch.bfloat16)
+            o = K.conv2x2_subpixel(xs, w4p, src, bias=bs, shadow=sh)
+            return torch.cat([o.flatten(), sh.float().flatten()])
+        out[f"conv2x2_subpixel f32 {cin}->64"] = spx32
     xh = r(2, 19, 21, 128)
     nw, nb, cw, cb = r(128, sc=0.5), r(128, sc=0.1), r(3, 128, 3, 3, sc=0.05), r(3, sc=0.1)
     out["dcae_head 2x19x21"] = lambda: K.dcae_head(xh, 1e-5, nw, nb, cw, cb)
