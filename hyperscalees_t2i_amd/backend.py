@@ -349,6 +349,7 @@ class VarConfig:
     lora_b_std: float = 0.02
     vae_chunk: int = 16
     native_attention: bool = True           # eggroll_qk_l2norm_kv + eggroll_flash_attention (False: F.normalize + SDPA)
+    native_vae_conv: bool = True            # VQVAE decoder 3x3 convs / GroupNorm on libeggroll (False: MIOpen + im2col)
 
 
 class VarBackend(ESBackend):
@@ -365,7 +366,8 @@ class VarBackend(ESBackend):
         c = self.cfg
         self.es_model = VARClassGenerator(model_depth=c.model_depth, device=self.device, arch=c.arch,
                                           weight_seed=c.weight_seed, vae_chunk=c.vae_chunk,
-                                          native_attention=c.native_attention)
+                                          native_attention=c.native_attention,
+                                          native_vae_conv=c.native_vae_conv)
         d = Path(c.ckpt_dir)
         vae_ckpt, var_ckpt = d / "vae_ch160v4096z32.pth", d / f"var_d{self.es_model.model_depth}.pth"
         if vae_ckpt.is_file() and var_ckpt.is_file():
@@ -699,6 +701,7 @@ class InfinityConfig:
     lora_seed: int = 1234
     weight_seed: int = 0
     synthetic_weights: bool = False          # no Infinity checkpoint loader: True is required (explicit opt-in)
+    native_vae_conv: bool = True             # the VAE's 160 / 320 / 640-wide 3x3 convs on eggroll_conv_nhwc (False: MIOpen)
 
 
 def synthetic_infinity_prompt_data(P: int = 4, lens: Tuple[int, int] = (16, 100), dim: int = 2048,
@@ -771,7 +774,8 @@ class InfinityBackend(ESBackend):
                                    top_p=float(c.top_p), cfg_insertion_layer=int(c.cfg_insertion_layer),
                                    sampling_per_bits=int(c.sampling_per_bits), device=self.device,
                                    synthetic_weights=c.synthetic_weights, arch=c.arch, weight_seed=c.weight_seed,
-                                   vae_chunk=c.vae_chunk, kv_budget_gb=c.kv_budget_gb)
+                                   vae_chunk=c.vae_chunk, kv_budget_gb=c.kv_budget_gb,
+                                   native_vae_conv=c.native_vae_conv)
         n = attach_lora(self.es_model.transformer, c.lora_r, c.lora_alpha, c.lora_target_modules)
         if n == 0:
             raise RuntimeError("no LoRA target module matched")

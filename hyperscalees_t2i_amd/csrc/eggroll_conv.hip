@@ -505,11 +505,14 @@ __device__ __forceinline__ void load_res_rows(u16x8 (&rv)[NR], const unsigned sh
         rv[it] = *reinterpret_cast<const u16x8*>(res + row_of(rbase + it * 8 + (lane >> 3)) * ldy + col0 + (lane & 7) * 8);
 }
 
-template <int ACT, class RowOf, bool RES = false, bool PRE = false>
+// NT: the tile may reach past the N = ldy output columns; a lane's 16-byte chunk of 8 columns is stored only
+// where it starts below N (N % 8 == 0 makes that chunk-exact).  The full-tile form has no such test.
+template <int ACT, class RowOf, bool RES = false, bool PRE = false, bool NT = false>
 __device__ __forceinline__ void store_tile_rows(f32x4 (&acc)[8][4], char* smem, int wave, int lane, int rbase,
                                                 int col0, unsigned short* __restrict__ Y, int64_t ldy, RowOf row_of,
                                                 const unsigned short* __restrict__ res = nullptr,
                                                 const u16x8* pre = nullptr) {
+    static_assert(!(NT && RES), "the column tail has no residual form");
     constexpr int ROWB = 128, SLOTS = 8;
     char* ctile = smem + wave * (128 * ROWB);
     const int r_l = lane & 15, c_l = (lane >> 4) * 4;
@@ -555,13 +558,20 @@ __device__ __forceinline__ void store_tile_rows(f32x4 (&acc)[8][4], char* smem, 
 #pragma unroll
             for (int u = 0; u < 8; ++u) v[it][u] = f32_to_bf16(bf16_to_f32(v[it][u]) + bf16_to_f32(rv[it][u]));
         }
+        if constexpr (NT) {
+            if (col0 + (lane & 7) * 8 >= ldy) continue;
+        }
         *reinterpret_cast<u16x8*>(Y + row_of(rbase + rr) * ldy + col0 + (lane & 7) * 8) = v[it];
     }
 }
 
 // WMW x WNW waves: (4, 2) 512 x 128 and (2, 4) 256 x 256 tiles run one 8-wave workgroup per CU
 // with the two wave groups staggered by a barrier (as the p8 kernels).
-template <int ACT, bool NORM, int WMW, int WNW>
+// NTAIL: the last column tile may be partial (N % BN != 0).  Weight rows at or past N are never addressed: their
+// DMA offset is the out-of-range one of the halo's padding, so the rows arrive as zeros while every wave still
+// issues NBW DMAs per K-step (hc_wait_n's counts hold); the bias addend clamps its column to N - 1; the store
+// drops the 16-byte chunks at or past N.  NTAIL = false is the full-tile kernel, instruction for instruction.
+template <int ACT, bool NORM, int WMW, int WNW, bool NTAIL = false>
 __global__ __launch_bounds__(512, 1) void k_conv3x3_halo(const unsigned short* __restrict__ X,
                                                          const unsigned short* __restrict__ Wt,
                                                          const unsigned short* __restrict__ bias, int H, int W,
@@ -571,6 +581,7 @@ __global__ __launch_bounds__(512, 1) void k_conv3x3_halo(const unsigned short* _
                                                          const unsigned short* __restrict__ res = nullptr) {
     using G = HC<WMW, WNW>;
     static_assert(halo_smem_bytes<G, NORM>() <= 160 * 1024, "LDS per CU");
+    static_assert(!(NTAIL && NORM), "the RMSNorm tail needs whole pixels in one tile");
     __shared__ __attribute__((aligned(16))) char smem[halo_smem_bytes<G, NORM>()];
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave / WNW, wn = wave % WNW;
@@ -604,7 +615,7 @@ __global__ __launch_bounds__(512, 1) void k_conv3x3_halo(const unsigned short* _
     for (int i = 0; i < G::NBW; ++i) {
         const int n = (i * G::NW + wave) * 16 + (lane >> 2);
         const int c = (lane & 3) ^ (((n >> 2) & 1) << 1);
-        boff[i] = (uint32_t)(((n0 + n) * K + c * 8) * 2);
+        boff[i] = !NTAIL || n0 + n < N ? (uint32_t)(((n0 + n) * K + c * 8) * 2) : 0x80000000u;
     }
     // fragment reads: A row f of the wave at tap (0,0) as a logical halo byte la, then the swizzled
     // byte of A row f at column shift dx (row shift dy = immediate dy * HS * 64)
@@ -729,7 +740,8 @@ __global__ __launch_bounds__(512, 1) void k_conv3x3_halo(const unsigned short* _
                                                          res, rv);
     } else {
         EGG_STAMP(4);
-        store_tile_rows<ACT>(acc, smem, wave, lane, wm * 128, n0 + wn * 64, Y, N, row_of);
+        store_tile_rows<ACT, decltype(row_of), false, false, NTAIL>(acc, smem, wave, lane, wm * 128, n0 + wn * 64, Y, N,
+                                                                    row_of);
     }
     EGG_STAMP_DRAIN();
     EGG_STAMP(5);
@@ -767,6 +779,25 @@ static bool halo_ok(int64_t ks, int64_t px, int64_t H, int64_t W, int64_t Cin, i
     return N % 256 == 0 && W % HC<2>::TWD == 0;
 }
 
+// The wide class: 3x3 px-1 convs at channel counts the rules above refuse (the VAR / Infinity VAE widths 160, 320,
+// 640): H % 16 == 0, Cin % 32 == 0 in [32, 2048] (the halo kernel walks Cin in 32-channel slices), N % 32 == 0,
+// on the halo kernel with a partial last column tile (NTAIL).  The tile: 512 x 128 needs W % 32 == 0, 256 x 256
+// W % 16 == 0; of those W allows, the one with the smaller padded width ceil(N / BN) * BN, a tie to 256 x 256.
+// Returns the tile's WMW (4: 512 x 128, 2: 256 x 256), 0 where the shape is outside the class.
+static int halo_wide_tile(int64_t ks, int64_t px, int64_t B, int64_t H, int64_t W, int64_t Cin, int64_t N) {
+    if (ks != 3 || px != 1 || B <= 0 || H <= 0 || W <= 0 || H % 16 || W % 16) return 0;
+    if (Cin < 32 || Cin > 2048 || Cin % 32 || N < 32 || N > 8192 || N % 32) return 0;
+    // 32-bit halo and weight offsets, a 31-bit grid (ceil(N / 128) <= 64 column tiles)
+    if (18 * (W + 2) * Cin * 2 >= (1ll << 31) || N * 9 * Cin * 2 >= (1ll << 31) || B * H * W >= (1ll << 31)) return 0;
+    const int64_t pad4 = (N + 127) / 128 * 128, pad2 = (N + 255) / 256 * 256;
+    return W % 32 == 0 && pad4 < pad2 ? 4 : 2;
+}
+
+// What conv_nhwc took before the wide class, as far as the channel counts go: those shapes keep their kernel.
+static bool conv_classic_channels(int64_t Cin, int64_t N) {
+    return N >= 64 && N % 64 == 0 && Cin >= 64 && (Cin & (Cin - 1)) == 0;
+}
+
 // The kernel selector of the _sel entry points (`fn` names the one called): 0 the halo kernel where halo_ok
 // and the tap-staged one elsewhere, 1 tap-staged, 2 halo (refused where it does not apply).
 static int conv_kernel_sel(const char* fn, int32_t kernel, int64_t ks, int64_t px, int64_t H, int64_t W, int64_t Cin,
@@ -781,18 +812,20 @@ static int conv_kernel_sel(const char* fn, int32_t kernel, int64_t ks, int64_t p
 }
 
 // k_conv3x3_halo over a halo_ok shape.  epi: 0 plain, 1 SiLU, 2 RMSNorm + residual; Epis: the ones the caller has.
-template <class Epis>
-static void launch_halo(Epis, int epi, const ConvArgs& a, hipStream_t st) {
+// wmw: the tile (4: 512 x 128, 2: 256 x 256); ntail: the last column tile is partial (the wide class only).
+template <class Epis, bool NTAIL = false>
+static void launch_halo(Epis, int epi, const ConvArgs& a, hipStream_t st, int wmw,
+                        std::bool_constant<NTAIL> = std::bool_constant<false>{}) {
     dispatch_int(epi, Epis{}, [&](auto E) {
-        dispatch_int(a.N == 128 ? 4 : 2, std::integer_sequence<int, 4, 2>{}, [&](auto WM) {
+        dispatch_int(wmw, std::integer_sequence<int, 4, 2>{}, [&](auto WM) {
             constexpr int EPI = decltype(E)::value, WMW = decltype(WM)::value;
             using G = HC<WMW>;
-            const int64_t tiles = a.B * (a.H / 16) * (a.W / G::TWD), tn = a.N / G::BN;
-            hipLaunchKernelGGL((k_conv3x3_halo<int(EPI == 1), EPI == 2, WMW, 8 / WMW>), dim3((unsigned)(tiles * tn)),
-                               dim3(64 * G::NW), 0, st, (const unsigned short*)a.x, (const unsigned short*)a.w,
-                               (const unsigned short*)a.bias, (int)a.H, (int)a.W, (int)a.Cin, (int)a.N, (int)tn,
-                               (unsigned short*)a.y, a.eps, (const unsigned short*)a.nw, (const unsigned short*)a.nb,
-                               (const unsigned short*)a.res);
+            const int64_t tiles = a.B * (a.H / 16) * (a.W / G::TWD), tn = (a.N + G::BN - 1) / G::BN;
+            hipLaunchKernelGGL((k_conv3x3_halo<int(EPI == 1), EPI == 2, WMW, 8 / WMW, NTAIL>),
+                               dim3((unsigned)(tiles * tn)), dim3(64 * G::NW), 0, st, (const unsigned short*)a.x,
+                               (const unsigned short*)a.w, (const unsigned short*)a.bias, (int)a.H, (int)a.W,
+                               (int)a.Cin, (int)a.N, (int)tn, (unsigned short*)a.y, a.eps, (const unsigned short*)a.nw,
+                               (const unsigned short*)a.nb, (const unsigned short*)a.res);
         });
     });
 }
@@ -866,8 +899,21 @@ int eggroll_conv_nhwc_sel(const void* x, const void* w_packed, const void* bias,
     EGG_CHECK_ARG(act == 0 || act == 2, "conv_nhwc: act must be 0 (none) or 2 (silu) (got %d)", act);
     const int64_t Ho = H + 3 - ks, Wo = W + 3 - ks;
     EGG_CHECK_ARG(B > 0 && H > 0 && W > 0 && Wo % px == 0, "conv_nhwc: bad B/H/W (output width %% px == 0 required)");
-    EGG_CHECK_ARG(N >= 64 && N % 64 == 0 && N <= 8192, "conv_nhwc: N=%lld must be a multiple of 64 (<= 8192)",
-                  (long long)N);
+    // the wide class (halo_wide_tile) is decided first: gemm8_geom's power-of-two Cin is the tap-staged kernel's rule
+    if (const int wmw = conv_classic_channels(Cin, N) ? 0 : halo_wide_tile(ks, px, B, H, W, Cin, N)) {
+        EGG_CHECK_ARG(kernel == 0 || kernel == 2,
+                      "conv_nhwc: Cin=%lld, N=%lld run on the halo kernel only: kernel must be 0 or 2 (got %d)",
+                      (long long)Cin, (long long)N, kernel);
+        EGG_CHECK_ARG(x && w_packed && y, "conv_nhwc: NULL pointer");
+        const ConvArgs a{x, w_packed, bias, B, H, W, Cin, N, y};
+        using PlainSilu = std::integer_sequence<int, 0, 1>;
+        if (N % (wmw == 4 ? 128 : 256) == 0) launch_halo(PlainSilu{}, act != 0, a, as_stream(stream), wmw);
+        else launch_halo(PlainSilu{}, act != 0, a, as_stream(stream), wmw, std::true_type{});
+        EGG_CHECK_LAUNCH("conv_nhwc");
+        return EGGROLL_OK;
+    }
+    EGG_CHECK_ARG(N >= 64 && N % 64 == 0 && N <= 8192, "conv_nhwc: N=%lld must be a multiple of 64 (<= 8192), or of 32 "
+                  "in the wide class (see include/eggroll.h)", (long long)N);
     // Cout = 128 at px 1 (3x3): the 512 x 128 tile (no zero MACs); everything else 256 x 256
     const bool tall = ks == 3 && px == 1 && N == 128;
     Gemm8Geom g;
@@ -877,7 +923,7 @@ int eggroll_conv_nhwc_sel(const void* x, const void* w_packed, const void* bias,
     if (int rc = conv_kernel_sel("conv_nhwc", kernel, ks, px, H, W, Cin, N, &halo)) return rc;
     const ConvArgs a{x, w_packed, bias, B, H, W, Cin, N, y};
     const int silu = act != 0;
-    if (halo) launch_halo(std::integer_sequence<int, 0, 1>{}, silu, a, as_stream(stream));
+    if (halo) launch_halo(std::integer_sequence<int, 0, 1>{}, silu, a, as_stream(stream), tall ? 4 : 2);
     else launch_gemm8(ConvIds{}, gemm8_id(px, silu, false, ks, tall ? 4 : 2), a, g, SubpixArgs{}, as_stream(stream));
     EGG_CHECK_LAUNCH("conv_nhwc");
     return EGGROLL_OK;
@@ -938,7 +984,7 @@ int eggroll_conv3x3_rmsnorm_nhwc_sel(const void* x, const void* w_packed, const 
     bool halo;
     if (int rc = conv_kernel_sel("conv3x3_rmsnorm_nhwc", kernel, 3, px, H, W, Cin, N, &halo)) return rc;
     const ConvArgs a{x, w_packed, bias, B, H, W, Cin, N, y, eps, norm_w, norm_b, res};
-    if (halo) launch_halo(std::integer_sequence<int, 2>{}, 2, a, as_stream(stream));
+    if (halo) launch_halo(std::integer_sequence<int, 2>{}, 2, a, as_stream(stream), tall ? 4 : 2);
     else launch_gemm8(NormIds{}, gemm8_id(px, 0, true, 3, tall ? 4 : 2), a, g, SubpixArgs{}, as_stream(stream));
     EGG_CHECK_LAUNCH("conv3x3_rmsnorm_nhwc");
     return EGGROLL_OK;

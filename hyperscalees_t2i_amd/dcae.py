@@ -93,6 +93,20 @@ def conv_gemm_px(c: int) -> int:
     return 1
 
 
+# (cin, cout, H, W) of wide-class shapes that keep their host's previous route: the per-shape A/B against that
+# route (profiles/conv_wide_vs_parent_ab.jsonl) did not show the halo kernel faster beyond the rounds' spread.
+# Empty: at 16 images every VAR and Infinity decoder shape measured faster, the closest 640 -> 640 at 16 x 16
+# (0.092 ms worst round against the im2col GEMM's 0.142 ms best round).
+CONV_HALO_WIDE_KEEP_PARENT: frozenset = frozenset()
+
+
+def conv_halo_wide_ok(cin: int, cout: int, H: int, W: int) -> bool:
+    """Whether a cin -> cout 3x3 conv (stride 1, pad 1) over an H x W map is in the wide class of libeggroll's
+    halo conv (kernels.conv_halo_wide_tile: the widths conv_gemm_px refuses, such as 160 / 320 / 640) and the
+    hosts should send it there."""
+    return K.conv_halo_wide_tile(cin, cout, H, W) != 0 and (cin, cout, H, W) not in CONV_HALO_WIDE_KEEP_PARENT
+
+
 class ResBlock(nn.Module):
     """conv1 (+bias, SiLU) -> conv2 (no bias) -> RMSNorm + residual.  Both convs run as libeggroll's
     implicit-GEMM MFMA kernel (bias + SiLU fused into conv1's epilogue) when the width allows,

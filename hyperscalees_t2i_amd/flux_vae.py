@@ -6,7 +6,8 @@ a single-head attention in the mid block, nearest x2 upsampling + 3x3 conv; scal
 Reference: `ZImagePipeline` decodes `latents / scaling_factor + shift_factor` with its `vae`
 (models/zImageTurbo.py:96-101).  Restated from the published config; no weights offline, parity with
 diffusers UNPINNED.  Execution: the dense 3x3 convs whose widths fit run as libeggroll's implicit-GEMM
-MFMA kernel (eggroll_conv_nhwc), conv_in / conv_out (16 / 3 channels) and the 1x1 shortcut on MIOpen /
+MFMA kernel (eggroll_conv_nhwc: power-of-two widths, and the Infinity BSQ-VAE's 160 / 320 / 640 through its wide
+class), conv_in / conv_out (16 / 3 channels) and the 1x1 shortcut on MIOpen /
 hipBLASLt, GroupNorm + SiLU on eggroll_group_norm_nhwc (fp32 statistics), the mid-block attention on SDPA.
 """
 from __future__ import annotations
@@ -19,7 +20,7 @@ import torch.nn.functional as F
 from torch import nn
 
 from . import kernels as K
-from .dcae import conv_gemm_px, nchw, nhwc
+from .dcae import conv_gemm_px, conv_halo_wide_ok, nchw, nhwc
 from .lora import LoRALinear
 
 
@@ -53,10 +54,12 @@ class Conv(nn.Module):
         self.weight = _p(cout, cin, ks, ks)
         self.bias = _p(cout)
         self.packed = None
+        self.native_wide_conv = True   # widths outside conv_gemm_px (160 / 320 / 640) on the halo conv's wide class
 
     def forward(self, x):
         cin, cout = self.weight.shape[1], self.weight.shape[0]
-        if self.ks == 3 and conv_gemm_px(cin) == 1 and cout % 64 == 0:
+        if self.ks == 3 and (conv_gemm_px(cin) == 1 and cout % 64 == 0 or self.native_wide_conv and x.is_cuda
+                             and conv_halo_wide_ok(cin, cout, x.shape[1], x.shape[2])):
             key = (self.weight._version, self.weight.data_ptr())
             if self.packed is None or self.packed[0] != key:
                 self.packed = (key, K.pack_conv3x3_weight(self.weight, 1))
@@ -110,6 +113,7 @@ class FluxVAEDecoder(nn.Module):
         self.scaling_factor, self.shift_factor = scaling_factor, shift_factor
         rev = list(reversed(widths))
         self.conv_in = Conv(latent_channels, rev[0])
+        self.conv_in.native_wide_conv = False   # 14 .. 64 latent channels: stays on MIOpen
         self.mid = nn.ModuleList([ResnetBlock(rev[0], rev[0]), MidAttention(rev[0]), ResnetBlock(rev[0], rev[0])])
         ups = []
         prev = rev[0]
@@ -122,6 +126,12 @@ class FluxVAEDecoder(nn.Module):
         self.up_blocks = nn.ModuleList(ups)
         self.conv_norm_out = GroupNorm(widths[0])
         self.conv_out = Conv(widths[0], 3)
+
+    def set_native_wide_conv(self, on: bool):
+        """False: the 3x3 convs at widths outside conv_gemm_px go back to MIOpen (A/B baseline)."""
+        for m in self.modules():
+            if isinstance(m, Conv) and m is not self.conv_in:
+                m.native_wide_conv = bool(on)
 
     @torch.no_grad()
     def init_weights(self, seed: int = 2):

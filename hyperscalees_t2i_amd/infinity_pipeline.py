@@ -148,7 +148,7 @@ class InfinityES:
                  device: str = "cuda:0", DTYPE: torch.dtype = torch.bfloat16, sigma_data: float = 0.5,
                  # build knobs
                  synthetic_weights: bool = False, arch=None, weight_seed: int = 0, vae_chunk: int = 16,
-                 kv_budget_gb: float = 120.0):
+                 kv_budget_gb: float = 120.0, native_vae_conv: bool = True):
         os.environ["TOKENIZERS_PARALLELISM"] = "false"
         self.device, self.DTYPE, self.bf16 = device, torch.bfloat16, bool(bf16)
         if float(h_div_w_template) != 1.0:
@@ -171,6 +171,7 @@ class InfinityES:
         self.text_encoder_ckpt = text_encoder_ckpt
         self.infinity = InfinityTransformer(a).to(device)
         self.vae = infinity_vae(a).to(device)
+        self.vae.set_native_wide_conv(native_vae_conv)   # 160 / 320 / 640-wide 3x3 convs on libeggroll (False: MIOpen)
         if synthetic_weights:
             self.infinity.init_weights(weight_seed)
             self.vae.init_weights(weight_seed + 2)

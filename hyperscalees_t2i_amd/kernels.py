@@ -1040,6 +1040,28 @@ def pack_conv3x3_weight(w: torch.Tensor, px: int) -> torch.Tensor:
     return out.reshape(px * Cout, ks * tw * Cin).contiguous()
 
 
+def conv_classic_channels(cin: int, n: int) -> bool:
+    """The channel counts eggroll_conv_nhwc takes at any map size (tap-staged kernel, or halo where its tiles are
+    full): Cin a power of two in [64, 2048], N a multiple of 64 up to 8192."""
+    return 64 <= n <= 8192 and n % 64 == 0 and 64 <= cin <= 2048 and cin & (cin - 1) == 0
+
+
+def conv_halo_wide_tile(cin: int, n: int, H: int, W: int, B: int = 1) -> int:
+    """eggroll_conv_nhwc's wide class (include/eggroll.h): 3x3 px-1 convs at channel counts outside the classic
+    rule (Cin a power of two >= 64, N % 64 == 0), on the halo kernel with a partial last column tile.  Returns
+    the tile's column width BN (128: the 512 x 128 tile, 256: 256 x 256), 0 where the shape is not in the class."""
+    if conv_classic_channels(cin, n):
+        return 0   # dispatched as before the class existed
+    if B <= 0 or H <= 0 or W <= 0 or H % 16 or W % 16:
+        return 0
+    if cin < 32 or cin > 2048 or cin % 32 or n < 32 or n > 8192 or n % 32:
+        return 0
+    if 18 * (W + 2) * cin * 2 >= 1 << 31 or n * 9 * cin * 2 >= 1 << 31 or B * H * W >= 1 << 31:
+        return 0
+    pad128, pad256 = -(-n // 128) * 128, -(-n // 256) * 256
+    return 128 if W % 32 == 0 and pad128 < pad256 else 256
+
+
 def conv_nhwc(x: torch.Tensor, w_packed: torch.Tensor, bias: Optional[torch.Tensor], ks: int, px: int = 1,
               act: Optional[str] = None, out: Optional[torch.Tensor] = None, kernel: int = 0) -> torch.Tensor:
     """ks x ks conv (ks 2 or 3), zero pad 1, of x [B,H,W,Cin] NHWC bf16 -> [B, H+3-ks, W+3-ks, N/px].
@@ -1056,6 +1078,8 @@ def conv_nhwc(x: torch.Tensor, w_packed: torch.Tensor, bias: Optional[torch.Tens
         if bias.numel() != N:
             raise ValueError(f"conv: bias has {bias.numel()} entries, need {N}")
     Ho, Wo, Cout = H + 3 - ks, W + 3 - ks, N // px
+    if ks == 3 and px == 1 and kernel == 1 and conv_halo_wide_tile(Cin, N, H, W, B):
+        raise RuntimeError(f"conv: Cin={Cin}, N={N} run on the halo kernel only (kernel 0 or 2), got kernel=1")
     if out is None:
         out = torch.empty((B, Ho, Wo, Cout), dtype=torch.bfloat16, device=x.device)
     e0 = OpTimer.begin()

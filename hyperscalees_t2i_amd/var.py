@@ -40,6 +40,7 @@ import torch.nn.functional as F
 from torch import nn
 
 from . import kernels as K
+from .dcae import conv_halo_wide_ok
 from .lora import LoRALinear, PopulationContext, set_population
 
 VAR_LORA_TARGETS = ["mat_qkv", "proj", "fc1", "fc2", "ada_lin.1", "head_nm.ada_lin.1", "head"]  # unifed_es.py:406
@@ -199,10 +200,30 @@ class DConv2d(nn.Conv2d):
     """nn.Conv2d (same parameters) whose small-map launches run as an explicit im2col GEMM.  The
     reference asks for deterministic convolutions (models/VAR.py:80-81); on this stack MIOpen's bf16
     solvers for the 16x16 maps at 640 channels differ run to run (tools/var_det_probe.py) and its
-    deterministic mode finds no algorithm for them, so maps of <= 32x32 pixels take the GEMM path."""
+    deterministic mode finds no algorithm for them, so maps of <= 32x32 pixels take the GEMM path.
+    Inside a native VQDecoder the 3x3 launches that libeggroll's conv takes (native_ok) leave both routes for
+    its halo-staged implicit GEMM, which is bitwise repeatable."""
+
+    native = False   # set by VQDecoder(native=True): eligible 3x3 launches run libeggroll's conv
+
+    def native_ok(self, x) -> bool:
+        """A 3x3 launch libeggroll's implicit-GEMM conv takes: bf16 channels-last on the GPU, at the classic
+        power-of-two widths or in the halo kernel's wide class (160 / 320 / 640; dcae.conv_halo_wide_ok)."""
+        N, C, H, W = x.shape
+        co = self.out_channels
+        return (self.native and self.kernel_size == (3, 3) and x.is_cuda and x.dtype == torch.bfloat16
+                and self.weight.dtype == torch.bfloat16
+                and (K.conv_classic_channels(C, co) or conv_halo_wide_ok(C, co, H, W)))
 
     def forward(self, x):
         N, C, H, W = x.shape
+        if self.native_ok(x):
+            key = (self.weight._version, self.weight.data_ptr())
+            if getattr(self, "_pk_key", None) != key:   # packed per parameter version (as flux_vae.Conv)
+                self._pk, self._pk_key = K.pack_conv3x3_weight(self.weight.detach(), 1), key
+            # the NHWC view of the channels-last map: contiguous as it stands, no copy
+            y = K.conv3x3_nhwc(x.permute(0, 2, 3, 1).contiguous(), self._pk, self.bias, 1)
+            return y.permute(0, 3, 1, 2)
         if H * W > 1024:
             return super().forward(x)
         wf = getattr(self, "_wflat", None)
@@ -218,8 +239,25 @@ class DConv2d(nn.Conv2d):
         return y.view(N, self.out_channels, H, W)
 
 
+class DGroupNorm(nn.GroupNorm):
+    """nn.GroupNorm (same parameters).  `native` (set by VQDecoder(native=True)): bf16 channels-last input runs
+    eggroll_group_norm_nhwc on its NHWC view (fp32 statistics), with the following SiLU fused when asked."""
+
+    native = False
+
+    def forward(self, x, silu: bool = False):
+        C = x.shape[1]
+        if (self.native and x.is_cuda and x.dtype == torch.bfloat16 and self.weight.dtype == torch.bfloat16
+                and C % 8 == 0 and C <= 2048):
+            y = K.group_norm_nhwc(x.permute(0, 2, 3, 1).contiguous(), self.num_groups, self.weight, self.bias,
+                                  self.eps, silu)
+            return y.permute(0, 3, 1, 2)
+        y = super().forward(x)
+        return F.silu(y) if silu else y
+
+
 def _norm(c: int) -> nn.GroupNorm:
-    return nn.GroupNorm(32, c, eps=1e-6, affine=True)
+    return DGroupNorm(32, c, eps=1e-6, affine=True)
 
 
 class ResnetBlock(nn.Module):
@@ -234,8 +272,8 @@ class ResnetBlock(nn.Module):
         self.nin_shortcut = DConv2d(cin, cout, 1) if cin != cout else nn.Identity()
 
     def forward(self, x):
-        h = self.conv1(F.silu(self.norm1(x)))
-        h = self.conv2(F.silu(self.norm2(h)))
+        h = self.conv1(self.norm1(x, silu=True))
+        h = self.conv2(self.norm2(h, silu=True))
         return self.nin_shortcut(x) + h
 
 
@@ -269,7 +307,7 @@ class Upsample2x(nn.Module):
 class VQDecoder(nn.Module):
     """basic_vae.py:163-226 (using_sa, using_mid_sa)."""
 
-    def __init__(self, ch: int, ch_mult: Sequence[int], num_res_blocks: int, z_channels: int):
+    def __init__(self, ch: int, ch_mult: Sequence[int], num_res_blocks: int, z_channels: int, native: bool = True):
         super().__init__()
         n = len(ch_mult)
         block_in = ch * ch_mult[-1]
@@ -294,6 +332,15 @@ class VQDecoder(nn.Module):
         self.norm_out = _norm(block_in)
         self.conv_out = DConv2d(block_in, 3, 3, 1, 1)
         self.n, self.nrb = n, num_res_blocks
+        self.set_native(native)
+
+    def set_native(self, on: bool):
+        """True: the eligible 3x3 convs and every GroupNorm (+ SiLU) run on libeggroll; False: MIOpen / im2col and
+        nn.GroupNorm + F.silu, the A/B baseline.  1x1 convs, the attention and conv_out (3 channels) never move."""
+        self.native = bool(on)
+        for m in self.modules():
+            if isinstance(m, (DConv2d, DGroupNorm)):
+                m.native = self.native
 
     def forward(self, z):
         h = self.mid.block_2(self.mid.attn_1(self.mid.block_1(self.conv_in(z))))
@@ -305,7 +352,7 @@ class VQDecoder(nn.Module):
                     h = up.attn[i_block](h)
             if i_level != 0:
                 h = up.upsample(h)
-        return self.conv_out(F.silu(self.norm_out(h)))
+        return self.conv_out(self.norm_out(h, silu=True))
 
 
 class _Quantize(nn.Module):
@@ -330,12 +377,12 @@ class _Quantize(nn.Module):
 class VQVAEDecode(nn.Module):
     """VQVAE (vqvae.py:16-63) minus the encoder: keys quantize.*, post_quant_conv.*, decoder.*."""
 
-    def __init__(self, a: VARArch):
+    def __init__(self, a: VARArch, native_conv: bool = True):
         super().__init__()
         self.arch = a
         self.quantize = _Quantize(a)
         self.post_quant_conv = nn.Conv2d(a.Cvae, a.Cvae, 3, 1, 1)
-        self.decoder = VQDecoder(a.vae_ch, a.vae_ch_mult, a.vae_num_res_blocks, a.Cvae)
+        self.decoder = VQDecoder(a.vae_ch, a.vae_ch_mult, a.vae_num_res_blocks, a.Cvae, native=native_conv)
         for p in self.parameters():
             p.requires_grad_(False)
 
@@ -532,7 +579,7 @@ class VARClassGenerator:
 
     def __init__(self, model_depth: int = 16, device: str = "cuda:0", DTYPE: torch.dtype = torch.float16,
                  arch: Optional[VARArch] = None, num_classes: int = 1000, weight_seed: int = 0,
-                 vae_chunk: int = 16, native_attention: bool = True):
+                 vae_chunk: int = 16, native_attention: bool = True, native_vae_conv: bool = True):
         if arch is None:
             if model_depth not in {16, 20, 24, 30}:
                 raise ValueError("model_depth must be one of {16, 20, 24, 30}")
@@ -545,7 +592,7 @@ class VARClassGenerator:
         dev = torch.device(device)
         with torch.device(dev):
             self.var = VARTransformer(arch)
-            self.vae = VQVAEDecode(arch)
+            self.vae = VQVAEDecode(arch, native_conv=native_vae_conv)
         self.var.init_weights(weight_seed)
         self.vae.init_weights(weight_seed + 1)
         self._cast()

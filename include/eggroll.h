@@ -430,7 +430,18 @@ int eggroll_conv2x2_subpixel_nhwc(const void* x, const void* w_packed, const voi
 /* Kernel choice per call: 0 auto, 1 the tap-staged implicit GEMM (any shape above), 2 the halo-
  * staged kernel (ks 3, px 1, H % 16 == 0, and W % 32 == 0 with N == 128 or W % 16 == 0 with
  * N % 256 == 0: the input halo of a 16-row tile is staged once per 32-channel slice instead of once
- * per tap).  Auto picks 2 whenever the shape allows it.  Results agree to fp32 summation order.  */
+ * per tap).  Auto picks 2 whenever the shape allows it.  Results agree to fp32 summation order.
+ *
+ * The wide class (the VAR / Infinity VAE widths 160, 320, 640).  A shape whose channel counts the rules
+ * above refuse (Cin no power of two or below 64, or N % 64 != 0) is accepted, by both entry points, when
+ *   ks 3, px 1, H % 16 == 0, W % 16 == 0, 32 <= Cin <= 2048 with Cin % 32 == 0, 32 <= N <= 8192 with N % 32 == 0.
+ * It runs on the halo kernel, whose last column tile may then be partial: weight rows at or past N read as
+ * zeros and nothing is written outside [B, H, W, N].  plain and SiLU epilogues only (the RMSNorm entry points
+ * keep N = 128 / 256).  The tile: 512 x 128 (BN 128) needs W % 32 == 0, 256 x 256 (BN 256) W % 16 == 0; of the
+ * tiles W allows, the one with the smaller padded width ceil(N / BN) * BN, a tie going to 256 x 256.  So
+ * with W % 32 == 0, N = 640 runs exact on five 128-wide tiles, N = 320 at 83 % (384), N = 160 at 62.5 % (256).
+ * kernel 0 and 2 both mean this kernel for the class; 1 (tap-staged) is refused, it has no such form.
+ * Shapes the rules above accept run exactly as before; everything else is refused before any launch.     */
 int eggroll_conv_nhwc_sel(const void* x, const void* w_packed, const void* bias, int64_t B, int64_t H, int64_t W,
                           int64_t Cin, int64_t N, int32_t ks, int32_t px, int32_t act, void* y, int32_t kernel,
                           void* stream);

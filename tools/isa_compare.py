@@ -1,12 +1,13 @@
 """Kernel-by-kernel comparison of two builds' gfx950 assembly (the `*gfx950*.s` files that
 `hipcc --save-temps -c` leaves behind), for refactors that must not change the generated code.
 
-    python tools/isa_compare.py --old DIR --new DIR --out profiles/NAME.json [--brief]
+    python tools/isa_compare.py --old DIR --new DIR --out profiles/NAME.json [--brief] [--added REGEX]
 
 One row per kernel, one line each: old and new name, the code-object notes (VGPR / AGPR / SGPR counts,
 spills, private segment and LDS bytes), the instruction count and a SHA-256 of the instructions with symbol names and
 label numbers normalised.  Counts and hashes only — no instruction text.  Exit status 1 when the kernel
-sets do not match one to one or a kernel's notes differ.
+sets do not match one to one or a kernel's notes differ.  --added REGEX: kernels only the new build has whose
+name matches (new template instances) are listed under "added" with their notes instead of counting as a mismatch.
 """
 from __future__ import annotations
 
@@ -23,9 +24,9 @@ NOTES = {"vgpr": ".vgpr_count", "agpr": ".agpr_count", "sgpr": ".sgpr_count", "v
          "sgpr_spill": ".sgpr_spill_count", "private_segment": ".private_segment_fixed_size",
          "lds": ".group_segment_fixed_size"}
 
-# (pattern, replacement) pairs: old demangled kernel name -> its new name.  The halo conv lost its last template
-# argument (PAD; the padded form `true` is the one that stayed).
-RENAMES = [(re.compile(r"(k_conv3x3_halo<[^<>]*), true>"), r"\1>")]
+# (pattern, replacement) pairs: old demangled kernel name -> its new name.  The halo conv gained a last template
+# argument (NTAIL, the partial last column tile; the full-tile form `false` is the one that was there).
+RENAMES = [(re.compile(r"(k_conv3x3_halo<[^<>]*)>"), r"\1, false>")]
 
 
 def demangle(names):
@@ -72,6 +73,8 @@ def main():
     ap.add_argument("--out", type=Path, required=True)
     ap.add_argument("--brief", action="store_true",
                     help="a kernel whose notes, count and hash are all equal gets the row [name, instructions, sha256[:16]]")
+    ap.add_argument("--added", default=None, metavar="REGEX",
+                    help="kernels only the new build has are listed, not problems, where their name matches")
     a = ap.parse_args()
     old, new = load(a.old), load(a.new)
     table, bad, cols = [], [], (*NOTES, "instructions", "sha256")
@@ -89,10 +92,13 @@ def main():
         table.append({"kernel": dname, "old_name": o["name"], "new_name": n["name"] if nname != dname else None,
                       "old": [o[k] for k in cols], "new": [n[k] for k in cols] if o != dict(n, name=o["name"]) else None,
                       "hash_equal": o["sha256"] == n["sha256"]})
-    bad += [f"added: {d}" for d in new]
+    added = sorted(d for d in new if a.added and re.search(a.added, d))
+    bad += [f"added: {d}" for d in new if d not in added]
     differ = [r["kernel"] for r in table if not r["hash_equal"]]
     # one row per line; new_name / new are null where they equal old_name / old
     head = {"kernels": len(table), "problems": bad, "hash_differs": len(differ), "columns": cols}
+    if added:
+        head["added"] = {d: [new[d][k] for k in cols[:-1]] for d in added}
     lines = [json.dumps(r) for r in table]
     if a.brief:   # equal kernels first, four to a line; then the full rows of the rest
         same = [r for r in table if r["new"] is None and r["new_name"] is None]
