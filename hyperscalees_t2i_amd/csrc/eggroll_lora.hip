@@ -1057,213 +1057,11 @@ static int project(const void* X, int64_t ldx, const float* tp, int64_t ldt, int
     return EGGROLL_OK;
 }
 
-// ------------------------------------------------------------------------------------
-// Fused-projection variant of the 8-phase kernel (r <= 2, rows_per_member >= 256): T = X A_k^T is
-// computed inside the GEMM from the X fragments already in registers, so X is read from HBM once
-// per LoRA linear instead of twice (k_lora_project's pre-pass is gone).
-//   AK[k][16][K] bf16 (k_lora_ak): rows q < R hold hi(A_k[q]), rows R+q lo(A_k[q] - hi), rest 0.
-//   Per K-tile a 2 KiB AK block is DMA'd next to the half-tiles: LDS rows 0..7 = member a (the
-//   tile's first member), rows 8..15 = member b (the next one; a tile spans at most two).
-//   In phases 2 and 4 (resp. 6, 8) wave (wm, wn) runs one extra transposed MFMA per k-substep on
-//   its X fragment f = wn:  D[q][m] += AK[q, k] X[m, k]  -> 4 MFMA per K-tile per wave (+6.25 %).
-//   At the end T[m][q] = D[q] + D[R + q] (hi + lo) per member goes to LDS for the MFMA epilogue.
-// ------------------------------------------------------------------------------------
-struct p8f : G8<2> {  // the 256 x 256 geometry with the AK block appended to each K-tile buffer
-    static constexpr int AKB = 2048;                 // AK block per K-tile: 16 rows x 64 bf16
-    static constexpr int RK = G8<2>::BUF;            // AK region inside a buffer
-    static constexpr int BUF = G8<2>::BUF + AKB;     // 66 KiB per K-tile buffer
-    static constexpr int VMC = G8<2>::VMC + 1;       // the next K-tile's AK DMA is in flight with A0, B1, A1
-    static constexpr int TOFF = 2 * BUF;             // T rows after the ring: [256][4] fp32
-    static constexpr int LDS = TOFF + 256 * 4 * 4;   // 136 KiB
-};
-
-__global__ __launch_bounds__(256) void k_lora_ak(const float* __restrict__ theta_pop, int64_t ld_theta, int64_t offA,
-                                                 int R, int64_t K, int n_members, unsigned short* __restrict__ AK) {
-    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;  // one thread per 8 elements
-    const int64_t per_row = K / 8, total = (int64_t)n_members * 16 * per_row;
-    if (idx >= total) return;
-    const int64_t c = (idx % per_row) * 8;
-    const int row = (int)((idx / per_row) % 16);
-    const int k = (int)(idx / (per_row * 16));
-    u16x8 o;
-    if (row < 2 * R) {
-        const int q = row % R;
-        const float* A = theta_pop + (int64_t)k * ld_theta + offA + (int64_t)q * K + c;
-#pragma unroll
-        for (int u = 0; u < 8; ++u) {
-            const unsigned short hi = f32_to_bf16(A[u]);
-            o[u] = row < R ? hi : f32_to_bf16(A[u] - bf16_to_f32(hi));
-        }
-    } else {
-#pragma unroll
-        for (int u = 0; u < 8; ++u) o[u] = 0;
-    }
-    *reinterpret_cast<u16x8*>(AK + ((int64_t)k * 16 + row) * K + c) = o;
-}
-
-template <int R>
-__global__ __launch_bounds__(512, 1) void k_lora_gemm8f(
-    const unsigned short* __restrict__ X, int64_t ldx, const unsigned short* __restrict__ W, int64_t ldw,
-    const unsigned short* __restrict__ bias, const unsigned short* __restrict__ AK, const float* __restrict__ theta_pop,
-    int64_t ld_theta, int64_t offB, float scale, int rows_per_member, int n_members, int M, int N, int64_t K,
-    int tiles_n, unsigned short* __restrict__ Y, int64_t ldy) {
-    __shared__ __attribute__((aligned(16))) char smem[p8f::LDS];
-    using G = p8f;
-    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wm = wave >> 2, wn = wave & 3;
-    const TileIdx ti = p8_tile_index<256>(M, tiles_n);
-    const int m0 = ti.m * 256, n0 = ti.n * 256;
-
-    const Stage<2> sA0 = make_stage_a<G, 0>(m0, M - 1, ldx, wave, lane);
-    const Stage<2> sA1 = make_stage_a<G, 1>(m0, M - 1, ldx, wave, lane);
-    const Stage<2> sB0 = make_stage_b<G, 0>(n0, N - 1, ldw, wave, lane);
-    const Stage<2> sB1 = make_stage_b<G, 1>(n0, N - 1, ldw, wave, lane);
-    // AK DMA: one dword per lane per K-tile; wave w fills LDS AK rows 2w, 2w+1 (swizzled like the tiles)
-    const int ma = m0 / rows_per_member;
-    const int mb = (ma + 1 < n_members) ? ma + 1 : ma;
-    uint32_t akoff;
-    {
-        const int row = 2 * wave + (lane >> 5), d = lane & 31, slot = d >> 2;
-        const int src_row = (row < 8 ? ma : mb) * 16 + (row & 7);
-        const int chunk = slot ^ (row & 7);
-        akoff = ((uint32_t)src_row * (uint32_t)K + chunk * 8 + (d & 3) * 2) * 2;
-    }
-    char* const e_buf = smem;
-    char* const o_buf = smem + G::BUF;
-    const __amdgpu_buffer_rsrc_t rX = __builtin_amdgcn_make_buffer_rsrc((void*)X, (short)0, 0x7fffffff, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rW = __builtin_amdgcn_make_buffer_rsrc((void*)W, (short)0, 0x7fffffff, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rK = __builtin_amdgcn_make_buffer_rsrc((void*)AK, (short)0, 0x7fffffff, 0x00020000);
-    auto issue_ak = [&](int kbytes, char* buf) {
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rK, (lds_void*)(buf + G::RK + wave * 256), 4, akoff, kbytes, 0, 0);
-    };
-
-    f32x4 acc[8][4];
-#pragma unroll
-    for (int i = 0; i < 8; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-    f32x4 tacc[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
-    bf16x8 a[4][2], b[2][2], ak[2];
-    int oA[2], oB[2], oK[2];
-    p8_frag_offsets(oA, wm * 64 + (lane & 15), lane);
-    p8_frag_offsets(oB, wn * 32 + (lane & 15), lane);
-    p8_frag_offsets(oK, lane & 15, lane);
-
-    auto tmma = [&](int h) {  // T-MFMA on this wave's X fragment f = wn (wave-uniform branches, no selects)
-        __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-        for (int kk = 0; kk < 2; ++kk) {
-            if (wn == 0) tacc[h] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ak[kk], a[0][kk], tacc[h], 0, 0, 0);
-            else if (wn == 1) tacc[h] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ak[kk], a[1][kk], tacc[h], 0, 0, 0);
-            else if (wn == 2) tacc[h] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ak[kk], a[2][kk], tacc[h], 0, 0, 0);
-            else tacc[h] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ak[kk], a[3][kk], tacc[h], 0, 0, 0);
-        }
-        __builtin_amdgcn_s_setprio(0);
-    };
-    auto read_ak = [&](const char* buf) {
-#pragma unroll
-        for (int kk = 0; kk < 2; ++kk) ak[kk] = *reinterpret_cast<const bf16x8*>(buf + G::RK + oK[kk]);
-    };
-
-    const int nk = (int)(K / BK);
-    auto kb = [nk](int t) -> int { return (t < nk ? t : nk - 1) * (BK * 2); };
-    issue(rX, sA0, 0, e_buf + G::RA0, wave);
-    issue(rW, sB1, 0, e_buf + G::RB1, wave);
-    issue_ak(0, e_buf);
-    issue(rX, sA1, 0, e_buf + G::RA1, wave);
-    issue(rW, sB0, 0, e_buf + G::RB0, wave);
-    issue(rX, sA0, kb(1), o_buf + G::RA0, wave);
-    issue(rW, sB1, kb(1), o_buf + G::RB1, wave);
-    issue_ak(kb(1), o_buf);
-    issue(rX, sA1, kb(1), o_buf + G::RA1, wave);
-    wait_vm<G::VMC>();  // K-tile 0 complete
-    P8_BAR();
-    if (wm == 1) P8_BAR();
-
-    // One K-tile in `buf` (the other buffer `oth`): as k_lora_gemm8, plus: AK read in phase 2/6 (last read
-    // -> restaged with B1 in phase 3/7), T-MFMA on A0 in phase 2/6 and on A1 in phase 4/8.  Phase 1 restages
-    // B0 of the next K-tile (kA, into `oth`), phases 2-4 the next-but-one (kB, into `buf`).
-    auto ktile = [&](char* buf, char* oth, int kA, int kB) __attribute__((always_inline)) {
-        p8_phase<G, 0, 0, 0, false, false, true>(acc, a, b, buf, oA, oB, oB, [&] { issue(rW, sB0, kA, oth + G::RB0, wave); });
-        p8_phase<G, 0, 1, 1, false, false, true>(
-            acc, a, b, buf, oA, oB, oB,
-            [&] {
-                read_ak(buf);
-                issue(rX, sA0, kB, buf + G::RA0, wave);
-            },
-            [&] { tmma(0); });
-        p8_phase<G, 1, 1, 2, false, false, true>(acc, a, b, buf, oA, oB, oB, [&] {
-            issue(rW, sB1, kB, buf + G::RB1, wave);
-            issue_ak(kB, buf);
-        });
-        p8_phase<G, 1, 0, 1, true, false, true>(
-            acc, a, b, buf, oA, oB, oB, [&] { issue(rX, sA1, kB, buf + G::RA1, wave); }, [&] { tmma(1); });
-    };
-    int t0 = 0;
-    for (; t0 + 1 < nk; t0 += 2) {
-        ktile(e_buf, o_buf, kb(t0 + 1), kb(t0 + 2));  // tile t0: restages t0+1 (odd) / t0+2 (even)
-        ktile(o_buf, e_buf, kb(t0 + 2), kb(t0 + 3));  // tile t0+1: restages t0+2 (even) / t0+3 (odd)
-    }
-    if (t0 < nk) ktile(e_buf, o_buf, kb(t0 + 1), kb(t0 + 2));
-    if (wm == 0) P8_BAR();
-    wait_vm<0>();
-    // T rows -> LDS: lanes 0-15 hold member a's D rows 0..3, lanes 32-47 member b's D rows 8..11
-    {
-        float* Tl = reinterpret_cast<float*>(smem + G::TOFF);
-        const int hq = lane >> 4;
-        if (hq == 0 || hq == 2) {
-            const int mem = hq >> 1;
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                const int rl = wm * 128 + h * 64 + wn * 16 + (lane & 15);
-#pragma unroll
-                for (int qq = 0; qq < R; ++qq) Tl[rl * 4 + mem * 2 + qq] = tacc[h][qq] + tacc[h][R + qq];
-            }
-        }
-    }
-    __syncthreads();
-    lora_mfma_addend<R, true>(acc, lane, m0, n0, wm * 128, wn * 64, bias,
-                              reinterpret_cast<const float*>(smem + G::TOFF), theta_pop, ld_theta, offB, scale,
-                              rows_per_member, M, N);
-    store_tile_t(acc, smem, wave, lane, m0, n0, wm * 128, wn * 64, M, N, Y, ldy);
-}
-
 // The instantiated kernels (dispatch_int, common.h).
 using RanksAll = std::integer_sequence<int, 0, 1, 2, 3, 4, 8, 16>;
 using RanksMF = std::integer_sequence<int, 0, 1, 2>;  // the MFMA-addend path
 using EpiOps = std::integer_sequence<int, EPI_NONE, EPI_SILU, EPI_RES, EPI_GATED, EPI_RES32, EPI_GATED32, EPI_GELU,
                                      EPI_MUL, EPI_GELU_ERF>;
-
-// The fused-projection kernel is opt-in (tile 12): measured at the Sana shapes it is 1-10 % SLOWER
-// than k_lora_project + k_lora_gemm8 (1.205 vs 1.189 ms at 131072x2240x2240, 5.82 vs 5.25 ms at
-// N = 11200) — the extra AK DMA and T-MFMA per K-tile cost more than the 10 % X re-read they save.
-static bool fused_ok(int tsel, int32_t r, int64_t K, int64_t rows_per_member) {
-    return tsel == 12 && (r == 1 || r == 2) && rows_per_member >= 256 && K % 64 == 0;
-}
-
-static int launch_gemm8f(const void* X, int64_t ldx, const void* W, int64_t ldw, const void* bias,
-                         const float* theta_pop, int64_t ld_theta, int64_t offA, int64_t offB, int32_t r, float scale,
-                         int64_t rows_per_member, int64_t M, int64_t N, int64_t K, void* Y, int64_t ldy, void* ws,
-                         hipStream_t st) {
-    const int64_t n_members = (M + rows_per_member - 1) / rows_per_member;
-    EGG_CHECK_ARG(M * ldx * 2 < (1ll << 31) && N * ldw * 2 < (1ll << 31) && n_members * 16 * K * 2 < (1ll << 31),
-                  "lora_linear_pop: operand > 2 GiB");
-    unsigned short* AK = reinterpret_cast<unsigned short*>(ws);
-    const int64_t work = n_members * 16 * (K / 8);
-    hipLaunchKernelGGL(k_lora_ak, dim3((unsigned)((work + 255) / 256)), dim3(256), 0, st, theta_pop, ld_theta, offA,
-                       (int)r, K, (int)n_members, AK);
-    EGG_CHECK_LAUNCH("lora_ak");
-    const int64_t tiles_m = (M + 255) / 256, tiles_n = (N + 255) / 256;
-    const dim3 grid((unsigned)(tiles_m * tiles_n));
-    dispatch_int(r, std::integer_sequence<int, 1, 2>{}, [&](auto R) {  // fused_ok: r is 1 or 2
-        hipLaunchKernelGGL((k_lora_gemm8f<decltype(R)::value>), grid, dim3(512), 0, st, (const unsigned short*)X, ldx,
-                           (const unsigned short*)W, ldw, (const unsigned short*)bias, AK, theta_pop, ld_theta, offB,
-                           scale, (int)rows_per_member, (int)n_members, (int)M, (int)N, K, (int)tiles_n,
-                           (unsigned short*)Y, ldy);
-    });
-    EGG_CHECK_LAUNCH("lora_gemm8f");
-    return EGGROLL_OK;
-}
 
 // The arguments every base-GEMM kernel takes, in kernel order.
 struct GemmArgs {
@@ -1464,15 +1262,14 @@ int eggroll_lora_delta_f32(const float* x, int64_t ldx, const float* A, int64_t 
 
 // Kernel choice is a per-call argument (no process-global state: the C-ABI is thread-safe per
 // stream).  0 = automatic: the 8-phase 256x256 kernel when the grid still fills the chip, else the
-// 128x128 one-barrier tile.  8 / 9 = 8-phase with MFMA / VALU LoRA epilogue, 12 = as 8 with the
-// projection fused (linear_pop only), 128 / 256 = one-barrier tiles.
+// 128x128 one-barrier tile.  8 / 9 = 8-phase 256x256 with MFMA / VALU LoRA epilogue, 10 = 8-phase
+// 256x320, 128 / 256 = one-barrier tiles.
 // Every argument check of the plain GEMM entry points, reported under the caller's name, before
 // anything is launched; *tsel: the kernel that will run.
 static int plain_args_ok(const char* api, int64_t ldx, int64_t ldw, int64_t ldy, int32_t r, int64_t rows_per_member,
                          int64_t M, int64_t N, int64_t K, int32_t kernel, int* tsel) {
-    EGG_CHECK_ARG(kernel == 0 || kernel == 8 || kernel == 9 || kernel == 10 || kernel == 12 || kernel == 128 ||
-                      kernel == 256,
-                  "%s: kernel must be 0 (auto), 8, 9, 10, 12, 128 or 256 (got %d)", api, kernel);
+    EGG_CHECK_ARG(kernel == 0 || kernel == 8 || kernel == 9 || kernel == 10 || kernel == 128 || kernel == 256,
+                  "%s: kernel must be 0 (auto), 8, 9, 10, 128 or 256 (got %d)", api, kernel);
     EGG_CHECK_ARG(M >= 0 && N > 0 && K > 0, "%s: bad sizes M=%lld N=%lld K=%lld", api, (long long)M, (long long)N,
                   (long long)K);
     EGG_CHECK_ARG(K % 64 == 0, "%s: K=%lld must be a multiple of 64", api, (long long)K);
@@ -1480,7 +1277,7 @@ static int plain_args_ok(const char* api, int64_t ldx, int64_t ldw, int64_t ldy,
     EGG_CHECK_ARG(rows_per_member > 0, "%s: rows_per_member must be > 0", api);
     *tsel = kernel ? kernel
                    : ((M / 256) * ((N + 255) / 256) >= 512 ? gemm8_auto(M, N, r, rows_per_member, EPI_NONE) : 128);
-    const bool p8 = *tsel == 8 || *tsel == 9 || *tsel == 10 || *tsel == 12;
+    const bool p8 = *tsel == 8 || *tsel == 9 || *tsel == 10;
     return gemm_args_ok(api, ldx, ldw, ldy, rows_per_member, M, N, K, p8);
 }
 
@@ -1495,7 +1292,7 @@ static int lora_gemm_launch(const char* api, int tsel, const void* X, int64_t ld
     const GemmArgs g{X, ldx, W, ldw, bias, T, theta_pop, ld_theta, offB, r, scale, rows_per_member, M, N, K, Y, ldy};
     if (tsel == 10 && gemm8n_ok(r, rows_per_member))  // else: kernel 8's VALU-epilogue path, as kernel 8 does
         return launch_gemm8<G8<2, 5>>(g, true, EPI_NONE, EpiArgs{}, st);
-    if (tsel == 8 || tsel == 9 || tsel == 10 || tsel == 12)
+    if (tsel == 8 || tsel == 9 || tsel == 10)
         return launch_gemm8<G8<2>>(g, tsel != 9 && r <= 2 && rows_per_member >= 256, EPI_NONE, EpiArgs{}, st);
     return tsel == 256 ? launch_gemm<kT256>(g, st) : launch_gemm<kT128>(g, st);
 }
@@ -1522,17 +1319,14 @@ int eggroll_lora_gemm_sel(const void* X, int64_t ldx, const void* W, int64_t ldw
                           const float* theta_pop, int64_t ld_theta, int64_t offB, int32_t r, float scale,
                           int64_t rows_per_member, int64_t M, int64_t N, int64_t K, void* Y, int64_t ldy,
                           int32_t kernel, void* stream) {
-    EGG_CHECK_ARG(kernel != 12, "lora_gemm_sel: kernel 12 fuses the projection (eggroll_lora_linear_pop_sel only)");
     return lora_gemm_impl(X, ldx, W, ldw, bias, T, theta_pop, ld_theta, offB, r, scale, rows_per_member, M, N, K, Y,
                           ldy, kernel, stream);
 }
 
 int64_t eggroll_lora_workspace_bytes(int64_t M, int64_t K, int32_t r, int64_t rows_per_member) {
     if (M <= 0 || r <= 0 || rows_per_member <= 0) return 0;
-    const int64_t t_bytes = M * r * 4;
-    const int64_t n_members = (M + rows_per_member - 1) / rows_per_member;
-    const int64_t ak_bytes = n_members * 16 * K * 2;
-    return t_bytes > ak_bytes ? t_bytes : ak_bytes;
+    (void)K;  // kept in the signature; the workspace is the fp32 T [M, r] alone
+    return M * r * 4;
 }
 
 int eggroll_lora_linear_pop_sel(const void* X, int64_t ldx, const void* W, int64_t ldw, const void* bias,
@@ -1546,18 +1340,12 @@ int eggroll_lora_linear_pop_sel(const void* X, int64_t ldx, const void* W, int64
     if (M == 0) return EGGROLL_OK;
     EGG_CHECK_ARG(X && W && Y, "lora_linear_pop: NULL pointer");
     EGG_CHECK_ARG(r == 0 || (theta_pop && T_ws), "lora_linear_pop: theta_pop / T_ws NULL with r > 0");
-    if (r > 0 && fused_ok(kernel, r, K, rows_per_member)) {  // projection fused into the 8-phase GEMM
-        // (launch_gemm8f checks the 32-bit offsets itself: it has a third operand, AK)
-        EGG_CHECK_ARG(ld_theta % 4 == 0 && offA % 4 == 0, "lora_linear_pop: theta offsets must be 16-byte aligned");
-        return launch_gemm8f(X, ldx, W, ldw, bias, theta_pop, ld_theta, offA, offB, r, scale, rows_per_member, M, N,
-                             K, Y, ldy, T_ws, as_stream(stream));
-    }
     if (r > 0) {
         int rc = eggroll_lora_project(X, ldx, theta_pop, ld_theta, offA, r, rows_per_member, M, K, T_ws, stream);
         if (rc) return rc;
     }
-    return lora_gemm_launch("lora_linear_pop", tsel == 12 ? 8 : tsel, X, ldx, W, ldw, bias, T_ws, theta_pop, ld_theta,
-                            offB, r, scale, rows_per_member, M, N, K, Y, ldy, stream);
+    return lora_gemm_launch("lora_linear_pop", tsel, X, ldx, W, ldw, bias, T_ws, theta_pop, ld_theta, offB, r, scale,
+                            rows_per_member, M, N, K, Y, ldy, stream);
 }
 
 // The epilogue GEMM with T = X A_k^T already computed (shared by linear_pop_epi and lora_gemm_epi).

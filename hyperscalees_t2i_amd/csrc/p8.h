@@ -232,11 +232,10 @@ __device__ __forceinline__ void p8_frag_offsets(int (&off)[2], int r0, int lane)
 // One phase: read the quadrant's fragments (RD: 0 = A+B, 1 = B only, 2 = A only; oB0 / oB1: the wave's
 // fragment bases in B0 / B1, the same array when both regions have PER0 rows), issue one region's
 // DMA (supplied by the caller), [early first K-tile wait], [vmcnt(VMC)], retire the reads, barrier,
-// the quadrant's MFMAs (+ the caller's `tail` MFMAs), barrier.
-template <class G, int QA, int QB, int RD, bool VM, bool EW, bool TR, class Issue, class Tail>
+// the quadrant's MFMAs, barrier.
+template <class G, int QA, int QB, int RD, bool VM, bool EW, bool TR, class Issue>
 __device__ __forceinline__ void p8_phase(f32x4 (&acc)[8][G::NF], bf16x8 (&a)[4][2], bf16x8 (&b)[G::NF0][2],
-                                         const char* buf, const int (&oA)[2], const int (&oB0)[2], const int (&oB1)[2], Issue&& issue_dma,
-                                         Tail&& tail) {
+                                         const char* buf, const int (&oA)[2], const int (&oB0)[2], const int (&oB1)[2], Issue&& issue_dma) {
     if (RD != 2) p8_read_b<(QB ? G::NF1 : G::NF0)>(b, buf + (QB ? G::RB1 : G::RB0), QB ? oB1 : oB0);
     if (RD != 1) p8_read_a(a, buf + (QA ? G::RA1 : G::RA0), oA);
     issue_dma();
@@ -245,13 +244,7 @@ __device__ __forceinline__ void p8_phase(f32x4 (&acc)[8][G::NF], bf16x8 (&a)[4][
     P8_LGKM0();
     P8_BAR();
     p8_mma<QA, QB, TR>(acc, a, b);
-    tail();
     P8_BAR();
-}
-template <class G, int QA, int QB, int RD, bool VM, bool EW, bool TR, class Issue>
-__device__ __forceinline__ void p8_phase(f32x4 (&acc)[8][G::NF], bf16x8 (&a)[4][2], bf16x8 (&b)[G::NF0][2],
-                                         const char* buf, const int (&oA)[2], const int (&oB0)[2], const int (&oB1)[2], Issue&& issue_dma) {
-    p8_phase<G, QA, QB, RD, VM, EW, TR>(acc, a, b, buf, oA, oB0, oB1, issue_dma, [] {});
 }
 
 }  // namespace eggroll

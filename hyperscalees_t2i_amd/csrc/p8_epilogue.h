@@ -270,9 +270,7 @@ __device__ __forceinline__ short bf16_bits(float f) { return (short)f32_to_bf16(
 //   L[m] = [Th_q (R) | Tl_q (R) | Th_q (R) | 1 | 0..]      R[n] = [sBh_q | sBh_q | sBl_q | bias | 0..]
 // with T = Th + Tl and s*B = sBh + sBl split into bf16 pairs, so the product is
 // Th.sBh + Tl.sBh + Th.sBl + bias: fp32-accurate to ~2^-16 relative (the Tl.sBl term is dropped).
-// TL: T comes from the fused projection's LDS rows [256][member a q0 q1 | member b q0 q1] instead of
-// the global [M][R] array of k_lora_project.
-template <int R, bool TL = false>
+template <int R>
 __device__ __forceinline__ void lora_mfma_addend(f32x4 (&acc)[8][4], int lane, int m0, int n0, int rbase, int cbase,
                                                  const unsigned short* __restrict__ bias, const float* __restrict__ T,
                                                  const float* __restrict__ theta_pop, int64_t ld_theta, int64_t offB,
@@ -313,7 +311,7 @@ __device__ __forceinline__ void lora_mfma_addend(f32x4 (&acc)[8][4], int lane, i
             if constexpr (R > 0) {
 #pragma unroll
                 for (int q = 0; q < R; ++q) {
-                    const float t = TL ? T[(row - m0) * 4 + h * 2 + q] : T[(int64_t)row * R + q];
+                    const float t = T[(int64_t)row * R + q];
                     const short th = bf16_bits(t);
                     v[q] = th;
                     v[R + q] = bf16_bits(t - bf16_to_f32((unsigned short)th));

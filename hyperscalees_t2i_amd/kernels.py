@@ -322,7 +322,8 @@ def lora_linear_pop(x: torch.Tensor, W: torch.Tensor, bias: Optional[torch.Tenso
 
     x: [M, K] bf16; W: [N, K] bf16; bias: [N] bf16 or None; theta_pop: [n_members, ld] fp32.
     r = 0 runs the plain base GEMM (no LoRA term).  kernel: 0 = automatic choice, else an explicit
-    kernel for A/B measurement (eggroll_lora_linear_pop_sel)."""
+    kernel for A/B measurement (eggroll_lora_linear_pop_sel): 8 / 9 the 256x256 8-phase kernel with the
+    MFMA / VALU LoRA epilogue, 10 the 256x320 8-phase kernel, 128 / 256 the one-barrier tiles."""
     _dev(x, "lora_linear_pop(x)", torch.bfloat16)
     _dev(W, "lora_linear_pop(W)", torch.bfloat16)
     M, K = x.shape
@@ -354,6 +355,27 @@ def lora_linear_pop(x: torch.Tensor, W: torch.Tensor, bias: Optional[torch.Tenso
 EPI = {None: 0, "silu": 1, "res": 2, "gated": 3, "res32": 4, "gated32": 5, "gelu": 6, "mul": 7, "gelu_erf": 8}
 
 
+def _epi_operands(fn: str, epi: Optional[str], M: int, N: int, res: Optional[torch.Tensor], gate: Optional[torch.Tensor],
+                  out: Optional[torch.Tensor], device: torch.device):
+    """The res / out / gate rules lora_linear_pop_epi and lora_gemm_epi share, errors under the caller's name `fn`:
+    (epilogue code, out, ldy, gate pointer, gate row stride, whether res is the fp32 stream)."""
+    code = EPI[epi]
+    f32res = code in (4, 5)
+    if res is not None:
+        _dev(res, f"{fn}(res)", torch.float32 if f32res else torch.bfloat16)
+        if res.shape[-1] != N or res.numel() != M * N:
+            raise ValueError(f"res {tuple(res.shape)} does not match [{M}, {N}]")
+    if f32res:
+        if res is None or (code == 5 and (gate is None or gate.dtype != torch.float32)):
+            raise ValueError(f"{fn}({epi}): needs an fp32 res (and an fp32 gate)")
+    elif out is None:
+        out = res if res is not None and code in (2, 3, 7) else torch.empty((M, N), dtype=torch.bfloat16, device=device)
+    # out is res (in place: contiguous, any leading shape) or a [M, N] view whose rows may be padded
+    ldy = N if out is None or out is res else _out_ld(out, f"{fn}(out)", M, N)
+    pg, gst = _row_ptr(gate, f"{fn}(gate)", N, allow_f32=code == 5) if gate is not None else (None, 0)
+    return code, out, ldy, pg, gst, f32res
+
+
 def lora_linear_pop_epi(x: torch.Tensor, W: torch.Tensor, bias: Optional[torch.Tensor], theta_pop: Optional[torch.Tensor],
                         offA: int, offB: int, r: int, scale: float, rows_per_member: int, epi: str,
                         res: Optional[torch.Tensor] = None, gate: Optional[torch.Tensor] = None,
@@ -369,20 +391,7 @@ def lora_linear_pop_epi(x: torch.Tensor, W: torch.Tensor, bias: Optional[torch.T
     _dev(W, "lora_linear_pop_epi(W)", torch.bfloat16)
     M, Kd = x.shape
     N = W.shape[0]
-    code = EPI[epi]
-    f32res = code in (4, 5)
-    if res is not None:
-        _dev(res, "lora_linear_pop_epi(res)", torch.float32 if f32res else torch.bfloat16)
-        if res.shape[-1] != N or res.numel() != M * N:
-            raise ValueError(f"res {tuple(res.shape)} does not match [{M}, {N}]")
-    if f32res:
-        if res is None or (code == 5 and (gate is None or gate.dtype != torch.float32)):
-            raise ValueError(f"lora_linear_pop_epi({epi}): needs an fp32 res (and an fp32 gate)")
-    elif out is None:
-        out = res if res is not None and code in (2, 3, 7) else torch.empty((M, N), dtype=torch.bfloat16, device=x.device)
-    # out is res (in place: contiguous, any leading shape) or a [M, N] view whose rows may be padded
-    ldy = N if out is None or out is res else _out_ld(out, "lora_linear_pop_epi(out)", M, N)
-    pg, gst = _row_ptr(gate, "lora_linear_pop_epi(gate)", N, allow_f32=code == 5) if gate is not None else (None, 0)
+    code, out, ldy, pg, gst, f32res = _epi_operands("lora_linear_pop_epi", epi, M, N, res, gate, out, x.device)
     if r > 0:
         _dev(theta_pop, "lora_linear_pop_epi(theta_pop)", torch.float32)
         need = lora_workspace_numel(M, Kd, r, rows_per_member)
@@ -405,22 +414,9 @@ def lora_gemm_epi(x: torch.Tensor, W: torch.Tensor, bias: Optional[torch.Tensor]
     _dev(W, "lora_gemm_epi(W)", torch.bfloat16)
     M, Kd = x.shape
     N = W.shape[0]
-    code = EPI[epi]
-    if code == 0:
+    if EPI[epi] == 0:
         raise ValueError("lora_gemm_epi: needs an epilogue op (use lora_gemm)")
-    f32res = code in (4, 5)
-    if res is not None:
-        _dev(res, "lora_gemm_epi(res)", torch.float32 if f32res else torch.bfloat16)
-        if res.shape[-1] != N or res.numel() != M * N:
-            raise ValueError(f"res {tuple(res.shape)} does not match [{M}, {N}]")
-    if f32res:
-        if res is None or (code == 5 and (gate is None or gate.dtype != torch.float32)):
-            raise ValueError(f"lora_gemm_epi({epi}): needs an fp32 res (and an fp32 gate)")
-    elif out is None:
-        out = res if res is not None and code in (2, 3, 7) else torch.empty((M, N), dtype=torch.bfloat16, device=x.device)
-    # out is res (in place: contiguous, any leading shape) or a [M, N] view whose rows may be padded
-    ldy = N if out is None or out is res else _out_ld(out, "lora_gemm_epi(out)", M, N)
-    pg, gst = _row_ptr(gate, "lora_gemm_epi(gate)", N, allow_f32=code == 5) if gate is not None else (None, 0)
+    code, out, ldy, pg, gst, f32res = _epi_operands("lora_gemm_epi", epi, M, N, res, gate, out, x.device)
     if r > 0:
         _dev(theta_pop, "lora_gemm_epi(theta_pop)", torch.float32)
         _dev(T, "lora_gemm_epi(T)", torch.float32)
@@ -432,22 +428,16 @@ def lora_gemm_epi(x: torch.Tensor, W: torch.Tensor, bias: Optional[torch.Tensor]
 
 
 def lora_workspace_numel(M: int, K: int, r: int, rows_per_member: int) -> int:
-    """fp32 elements of the eggroll_lora_linear_pop workspace (T, or the fused path's A_k images)."""
+    """fp32 elements of the eggroll_lora_linear_pop workspace: T = X A_k^T, [M, r] (K is ignored)."""
     nbytes = int(_lib.load().eggroll_lora_workspace_bytes(M, K, r, rows_per_member))
     return max(1, -(-nbytes // 4))
-
-
-def lora_fused(M: int, N: int, K: int, r: int, rows_per_member: int, kernel: int = 0) -> bool:
-    """True when eggroll_lora_linear_pop_sel runs the projection inside the 8-phase GEMM (mirrors
-    fused_ok in eggroll_lora.hip): only with kernel 12 — the automatic choice is the two-pass
-    k_lora_project + k_lora_gemm8, which measured faster at every Sana shape."""
-    return kernel == 12 and r in (1, 2) and rows_per_member >= 256 and K % 64 == 0
 
 
 def lora_gemm(x: torch.Tensor, W: torch.Tensor, bias: Optional[torch.Tensor], T: Optional[torch.Tensor],
               theta_pop: Optional[torch.Tensor], offB: int, r: int, scale: float, rows_per_member: int,
               out: Optional[torch.Tensor] = None, kernel: int = 0) -> torch.Tensor:
-    """The MFMA GEMM + fused LoRA epilogue alone, given T = X A_k^T (from lora_project)."""
+    """The MFMA GEMM + fused LoRA epilogue alone, given T = X A_k^T (from lora_project).
+    kernel: 0 automatic, 8 / 9 / 10 / 128 / 256 as lora_linear_pop (eggroll_lora_gemm_sel)."""
     _dev(x, "lora_gemm(x)", torch.bfloat16)
     _dev(W, "lora_gemm(W)", torch.bfloat16)
     M, K = x.shape
@@ -463,9 +453,10 @@ def lora_gemm(x: torch.Tensor, W: torch.Tensor, bias: Optional[torch.Tensor], T:
 
 
 def gemm_tile_for(M: int, N: int, r: int = 2, rows_per_member: int = 1 << 30, epi: Optional[str] = None) -> int:
-    """Kernel libeggroll's automatic choice uses for an M x N LoRA GEMM (mirrors lora_gemm_impl / gemm_epi_impl
+    """Kernel libeggroll's automatic choice uses for an M x N LoRA GEMM (mirrors plain_args_ok / gemm_epi_impl
     / gemm8_auto): 8 = the 8-phase 256x256 kernel, 10 = the 8-phase 256x320 kernel, 128 = the 128x128
-    one-barrier tile (no epilogue op only)."""
+    one-barrier tile (no epilogue op only).  It never returns 9 (kernel 8's tile with the VALU epilogue) or
+    256 (the 256x256 one-barrier tile), the other ids the selectors accept."""
     if epi is None and (M // 256) * ((N + 255) // 256) < 512:
         return 128
     if not (r == 0 or (r <= 2 and rows_per_member >= 256)) or epi in ("res", "gated", "mul"):

@@ -260,7 +260,7 @@ class LoRALinear(nn.Module):
                     ev[1].record()
                     GemmTimer.records.append((None, ev[0], ev[1], M, self.out_features, self.in_features, self.r, rpm,
                                               None))
-            elif GemmTimer.active:  # the same two kernels as lora_linear_pop's unfused path, timed apart
+            elif GemmTimer.active:  # the same two kernels as lora_linear_pop launches, timed apart
                 ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
                 T = ws[: M * self.r].view(M, self.r)
                 ev[0].record()
@@ -270,7 +270,7 @@ class LoRALinear(nn.Module):
                                 rpm)
                 ev[2].record()
                 GemmTimer.records.append((*ev, M, self.out_features, self.in_features, self.r, rpm, None))
-            else:  # projection T = X A_k^T + GEMM + LoRA epilogue (one fused kernel when eligible)
+            else:  # projection T = X A_k^T, then the GEMM + LoRA epilogue: two launches in one C call
                 y = K.lora_linear_pop(x2, self.weight, self.bias, ctx.theta_pop, self.theta_off_A, self.theta_off_B,
                                       self.r, self.scale, rpm, T_ws=ws)
         elif self.r:

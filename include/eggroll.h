@@ -200,8 +200,8 @@ int eggroll_lora_gemm_epi_sel(const void* X, int64_t ldx, const void* W, int64_t
  * (PEFT lora_A.weight / lora_B.weight row-major inside theta_k).
  * X, W, Y bf16 row-major (ldx, ldw, ldy in elements); bias bf16 or NULL; theta_pop fp32.
  * T_ws: workspace of >= eggroll_lora_workspace_bytes(M, K, r, rows_per_member) bytes,
- * 16-byte aligned (fp32 T [M, r] for the two-pass path; bf16 hi/lo A_k images [members][16][K]
- * when the projection is fused into the GEMM: tile 12 forced, r <= 2, rows_per_member >= 256).
+ * 16-byte aligned: the fp32 T [M, r], so M * r * 4 bytes (0 when M, r or rows_per_member <= 0);
+ * K is ignored and stays in the signature.
  * Requires K % 64 == 0, r <= 16, ldx/ldw % 8 == 0.                                        */
 int64_t eggroll_lora_workspace_bytes(int64_t M, int64_t K, int32_t r, int64_t rows_per_member);
 int eggroll_lora_linear_pop(const void* X, int64_t ldx, const void* W, int64_t ldw,
@@ -221,8 +221,8 @@ int eggroll_lora_gemm(const void* X, int64_t ldx, const void* W, int64_t ldw, co
  * measurement: 0 = automatic (as above: the 8-phase 256x256 kernel when the grid fills the chip,
  * else 128x128); 8 = 8-phase with the MFMA LoRA epilogue, 9 = 8-phase with a VALU epilogue,
  * 10 = 8-phase 256x320 tile with the MFMA LoRA epilogue (r <= 2 with rows_per_member >= 256, or
- * r = 0; bit-identical to 8), 128 / 256 = one-barrier tiles; linear_pop_sel also takes 12 = 8-phase
- * with the projection fused into the GEMM (opt-in: slower than the two-pass path at the Sana shapes). */
+ * r = 0; bit-identical to 8), 128 / 256 = one-barrier tiles.  Any other id (0, 8, 9, 10, 128, 256
+ * are all there are) is refused with EGGROLL_ERR_ARG before anything is launched.                   */
 int eggroll_lora_gemm_sel(const void* X, int64_t ldx, const void* W, int64_t ldw, const void* bias,
                           const float* T, const float* theta_pop, int64_t ld_theta, int64_t offB,
                           int32_t r, float scale, int64_t rows_per_member, int64_t M, int64_t N,

@@ -47,10 +47,25 @@ def test_argument_errors_are_reported():
                                          None, 11, None)  # kernel 11: not a kernel id
     assert rc == -1 and b"kernel" in lib.eggroll_last_error()
     rc = lib.eggroll_lora_gemm_sel(None, 64, None, 64, None, None, None, 0, 0, 2, 1.0, 10, 10, 10, 64, None, 10, 12,
-                                   None)  # kernel 12 (fused projection) exists only in linear_pop_sel
-    assert rc == -1 and b"12" in lib.eggroll_last_error()
+                                   None)  # kernel 12 (the removed fused-projection kernel) is not a kernel id
+    assert rc == -1 and lib.eggroll_last_error().startswith(b"lora_gemm: ")
+    assert b"0 (auto), 8, 9, 10, 128 or 256 (got 12)" in lib.eggroll_last_error()
+    rc = lib.eggroll_lora_linear_pop_sel(None, 64, None, 64, None, None, 0, 0, 0, 2, 1.0, 10, 10, 10, 64, None, 10,
+                                         None, 12, None)
+    assert rc == -1 and lib.eggroll_last_error().startswith(b"lora_linear_pop: ")
+    assert lib.eggroll_last_error().endswith(b"(got 12)")
     with pytest.raises(_lib.EggrollError):
         _lib.check(-1, "probe")
+
+
+def test_lora_workspace_is_the_projection_alone():
+    """eggroll_lora_workspace_bytes = M * r * 4, the fp32 T [M, r]; K is ignored."""
+    ws = _lib.load().eggroll_lora_workspace_bytes
+    assert ws(1000, 2240, 2, 300) == 8000
+    assert ws(8, 2240, 2, 1) == 64                      # 8 members of one row: more A_k image than T
+    assert ws(8, 64, 2, 1) == ws(8, 1 << 20, 2, 1)
+    assert ws(0, 2240, 2, 300) == 0 and ws(-1, 2240, 2, 300) == 0
+    assert ws(1000, 2240, 0, 300) == 0 and ws(1000, 2240, 2, 0) == 0
 
 
 def test_zero_sized_calls_are_noops():

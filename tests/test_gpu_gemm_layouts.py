@@ -164,12 +164,11 @@ def _run(c, layout, api, kernel, epi=None, inplace=False, y_null=False):
 
 
 # ---------------------------------------------------------------------------------- 1. plain GEMM, every tile kind
-PLAIN = ([(t, "S1", r) for t in (8, 10, 12) for r in (0, 1, 2)] +
+PLAIN = ([(t, "S1", r) for t in (8, 10) for r in (0, 1, 2)] +
          [(t, "S1", r) for t in (128, 256, 9) for r in (0, 2)] +
          [(t, "S2", r) for t in (128, 256, 9) for r in (3, 4)] +
-         [(t, "S2", 0) for t in (128, 256, 8, 9, 10, 12)])
-# kernel 12 fuses the projection: eggroll_lora_linear_pop_sel only (eggroll_lora_gemm_sel refuses it: test_refusals)
-PLAIN = [(t, s, r, api) for t, s, r in PLAIN for api in ("linear_pop", "gemm") if not (t == 12 and api == "gemm")]
+         [(t, "S2", 0) for t in (128, 256, 8, 9, 10)])
+PLAIN = [(t, s, r, api) for t, s, r in PLAIN for api in ("linear_pop", "gemm")]
 
 
 @pytest.mark.parametrize("tile,shape,r,api", PLAIN, ids=[f"tile{t}-{s}-r{r}-{a}" for t, s, r, a in PLAIN])
@@ -356,7 +355,7 @@ REFUSED = [
     ("rpg=0-gated32", EPI_EP, "gated32", dict(rpg=0)),
     ("K=96", PLAIN_EP + EPI_EP, "silu", dict(K=96, ldx=96, ldw=96)),
     ("kernel=7", PLAIN_EP + EPI_EP, "silu", dict(kernel=7)),
-    ("kernel=12-gemm_sel", ("eggroll_lora_gemm_sel",), None, dict(kernel=12)),
+    ("kernel=12", PLAIN_EP + EPI_EP, "silu", dict(kernel=12)),     # the removed fused-projection kernel
     ("kernel=9-epi", EPI_EP, "silu", dict(kernel=9)),
     ("r=3-epi", EPI_EP, "silu", dict(r=3)),
     ("r=2-rpm=255-epi", EPI_EP, "silu", dict(rpm=255)),

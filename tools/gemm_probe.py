@@ -14,18 +14,6 @@ from hyperscalees_t2i_amd import kernels as K  # noqa: E402
 from tools.gemm_probe_util import bench  # noqa: E402
 
 
-def _unused(fn, it=10):
-    fn()
-    torch.cuda.synchronize()
-    s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    s.record()
-    for _ in range(it):
-        fn()
-    e.record()
-    torch.cuda.synchronize()
-    return s.elapsed_time(e) / it
-
-
 rounds = int(sys.argv[1]) if len(sys.argv) > 1 else 3
 dev = torch.device("cuda:0")
 for (M, N, Kd, rpm) in [(8 * 16384, 2240, 2240, 16384), (8 * 4800, 2240, 2240, 4800), (8 * 16384, 11200, 2240, 16384)]:
@@ -39,7 +27,7 @@ for (M, N, Kd, rpm) in [(8 * 16384, 2240, 2240, 16384), (8 * 4800, 2240, 2240, 4
     res = {}
     ws = torch.empty(K.lora_workspace_numel(M, Kd, 2, rpm), device=dev)
     for _ in range(rounds):
-        for tile in (256, 9, 8):
+        for tile in (9, 8, 10):
             res.setdefault(f"gemm_t{tile}", []).append(bench(lambda: K.lora_gemm(x, W, b, T, tp, 2 * Kd, 2, 4.0, rpm, out=y, kernel=tile)))
         res.setdefault("linear_pop_auto", []).append(
             bench(lambda: K.lora_linear_pop(x, W, b, tp, 0, 2 * Kd, 2, 4.0, rpm, out=y, T_ws=ws)))

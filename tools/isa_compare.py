@@ -1,13 +1,14 @@
 """Kernel-by-kernel comparison of two builds' gfx950 assembly (the `*gfx950*.s` files that
 `hipcc --save-temps -c` leaves behind), for refactors that must not change the generated code.
 
-    python tools/isa_compare.py --old DIR --new DIR --out profiles/NAME.json [--brief] [--added REGEX]
+    python tools/isa_compare.py --old DIR --new DIR --out profiles/NAME.json [--brief] [--added REGEX] [--dropped REGEX]
 
 One row per kernel, one line each: old and new name, the code-object notes (VGPR / AGPR / SGPR counts,
 spills, private segment and LDS bytes), the instruction count and a SHA-256 of the instructions with symbol names and
 label numbers normalised.  Counts and hashes only — no instruction text.  Exit status 1 when the kernel
 sets do not match one to one or a kernel's notes differ.  --added REGEX: kernels only the new build has whose
-name matches (new template instances) are listed under "added" with their notes instead of counting as a mismatch.
+name matches (new template instances) are listed under "added" with their notes instead of counting as a mismatch;
+--dropped REGEX: the same for kernels only the old build has (removed kernels), listed under "dropped".
 """
 from __future__ import annotations
 
@@ -24,9 +25,9 @@ NOTES = {"vgpr": ".vgpr_count", "agpr": ".agpr_count", "sgpr": ".sgpr_count", "v
          "sgpr_spill": ".sgpr_spill_count", "private_segment": ".private_segment_fixed_size",
          "lds": ".group_segment_fixed_size"}
 
-# (pattern, replacement) pairs: old demangled kernel name -> its new name.  The halo conv gained a last template
-# argument (NTAIL, the partial last column tile; the full-tile form `false` is the one that was there).
-RENAMES = [(re.compile(r"(k_conv3x3_halo<[^<>]*)>"), r"\1, false>")]
+# (pattern, replacement) pairs: old demangled kernel name -> its new name, for a refactor that renames kernels or
+# adds template arguments, e.g. (re.compile(r"(k_name<[^<>]*)>"), r"\1, false>").  Empty: names pair as they are.
+RENAMES = []
 
 
 def demangle(names):
@@ -75,16 +76,21 @@ def main():
                     help="a kernel whose notes, count and hash are all equal gets the row [name, instructions, sha256[:16]]")
     ap.add_argument("--added", default=None, metavar="REGEX",
                     help="kernels only the new build has are listed, not problems, where their name matches")
+    ap.add_argument("--dropped", default=None, metavar="REGEX",
+                    help="kernels only the old build has are listed, not problems, where their name matches")
     a = ap.parse_args()
     old, new = load(a.old), load(a.new)
-    table, bad, cols = [], [], (*NOTES, "instructions", "sha256")
+    table, bad, dropped, cols = [], [], {}, (*NOTES, "instructions", "sha256")
     for dname, o in sorted(old.items()):
         nname = dname
         for pat, rep in RENAMES:
             nname = pat.sub(rep, nname)
         n = new.pop(nname, None)
         if n is None:
-            bad.append(f"dropped: {dname}")
+            if a.dropped and re.search(a.dropped, dname):
+                dropped[dname] = [o[k] for k in cols[:-1]]
+            else:
+                bad.append(f"dropped: {dname}")
             continue
         notes_equal = all(o[k] == n[k] for k in NOTES)
         if not notes_equal:
@@ -99,13 +105,16 @@ def main():
     head = {"kernels": len(table), "problems": bad, "hash_differs": len(differ), "columns": cols}
     if added:
         head["added"] = {d: [new[d][k] for k in cols[:-1]] for d in added}
+    if dropped:
+        head["dropped"] = dropped
     lines = [json.dumps(r) for r in table]
     if a.brief:   # equal kernels first, four to a line; then the full rows of the rest
         same = [r for r in table if r["new"] is None and r["new_name"] is None]
         short = [json.dumps([r["kernel"], r["old"][-2], r["old"][-1][:16]]) for r in same]
         lines = [", ".join(short[i:i + 4]) for i in range(0, len(short), 4)] + [json.dumps(r) for r in table if r not in same]
     a.out.write_text("{" + json.dumps(head)[1:-1] + ',\n"rows": [\n' + ",\n".join(lines) + "\n]}\n")
-    print(f"{len(table)} kernels matched, {len(differ)} differ in hash, {len(bad)} problems")
+    print(f"{len(table)} kernels matched, {len(differ)} differ in hash, {len(dropped)} dropped as expected, "
+          f"{len(bad)} problems")
     for b in bad:
         print("  " + b)
     for d in differ:
