@@ -350,6 +350,7 @@ class VarConfig:
     vae_chunk: int = 16
     native_attention: bool = True           # eggroll_qk_l2norm_kv + eggroll_flash_attention (False: F.normalize + SDPA)
     native_vae_conv: bool = True            # VQVAE decoder 3x3 convs / GroupNorm on libeggroll (False: MIOpen + im2col)
+    native_sampler: bool = True             # eggroll_sample_topk_topp, one launch per scale (False: torch ops + multinomial)
 
 
 class VarBackend(ESBackend):
@@ -367,7 +368,8 @@ class VarBackend(ESBackend):
         self.es_model = VARClassGenerator(model_depth=c.model_depth, device=self.device, arch=c.arch,
                                           weight_seed=c.weight_seed, vae_chunk=c.vae_chunk,
                                           native_attention=c.native_attention,
-                                          native_vae_conv=c.native_vae_conv)
+                                          native_vae_conv=c.native_vae_conv,
+                                          native_sampler=c.native_sampler)
         d = Path(c.ckpt_dir)
         vae_ckpt, var_ckpt = d / "vae_ch160v4096z32.pth", d / f"var_d{self.es_model.model_depth}.pth"
         if vae_ckpt.is_file() and var_ckpt.is_file():

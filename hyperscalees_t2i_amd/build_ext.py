@@ -18,7 +18,8 @@ BUILD = PKG / "_build"
 LIB = BUILD / "libeggroll.so"
 # the translation units of libeggroll: the one list (_lib.SOURCE_FILES and the tools derive theirs from it)
 SOURCES = ["eggroll_es.hip", "eggroll_lora.hip", "eggroll_conv.hip", "eggroll_nhwc.hip", "eggroll_norm.hip",
-           "eggroll_qk.hip", "eggroll_linattn.hip", "eggroll_attn.hip", "eggroll_gguf.hip", "eggroll_image.hip"]
+           "eggroll_qk.hip", "eggroll_linattn.hip", "eggroll_attn.hip", "eggroll_gguf.hip", "eggroll_image.hip",
+           "eggroll_sample.hip"]
 ARCH = "gfx950"
 
 

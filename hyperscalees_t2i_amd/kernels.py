@@ -789,6 +789,55 @@ def qk_l2norm_kv(q: Optional[torch.Tensor], k: Optional[torch.Tensor], v: Option
     OpTimer.end(e0, "qk_l2norm_kv", 4.0 * rows * heads * 64 * sum(t is not None for t in (q, k, v)), f"rows{rows}")
 
 
+def sample_topk_topp(cond: torch.Tensor, q: torch.Tensor, top_k: int = 0, top_p: float = 0.0,
+                     uncond: Optional[torch.Tensor] = None, w_cond: float = 1.0, w_uncond: float = 0.0,
+                     x_out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """eggroll_sample_topk_topp: one token per row of logits, one launch.  cond: [R, V] or [nb, rows, V] bf16 / fp32
+    view with unit inner stride (the 3-D form is a slice of a [nb, 2, rows, V] head output: rows ld apart, blocks
+    block_ld apart); uncond: None, or a view of the same shape, strides and dtype, and then the row sampled is
+    x = w_cond * cond - w_uncond * uncond (two roundings, as torch computes it).  top_k <= 0 or >= V: no top-k;
+    top_p <= 0: no top-p (the reference's conventions).  q: fp32 Exponential(1) draws, one per logit (contiguous, or
+    [R, V] with unit inner stride); x_out (optional, fp32, like q) receives x.  Returns idx int64, cond.shape[:-1];
+    -1 marks a row holding NaN / +inf or nothing finite."""
+    _dev(cond, "sample_topk_topp(cond)", contiguous=False)
+    if cond.dtype not in (torch.bfloat16, torch.float32):
+        raise _lib.EggrollError(f"sample_topk_topp(cond): expected bf16 or fp32, got {cond.dtype}")
+    if cond.dim() not in (2, 3) or cond.stride(-1) != 1:
+        raise ValueError(f"sample_topk_topp: cond {tuple(cond.shape)} / {cond.stride()} is no [R, V] or [nb, rows, V] "
+                         "view with unit inner stride")
+    V, rpb = int(cond.shape[-1]), int(cond.shape[-2])
+    nb = int(cond.shape[0]) if cond.dim() == 3 else 1
+    R = nb * rpb
+    ld = cond.stride(-2) if rpb > 1 else V
+    block_ld = cond.stride(0) if cond.dim() == 3 and nb > 1 else 0
+    if uncond is not None:
+        _dev(uncond, "sample_topk_topp(uncond)", cond.dtype, contiguous=False)
+        if uncond.shape != cond.shape or any(s > 1 and a != b for s, a, b in zip(cond.shape, cond.stride(), uncond.stride())):
+            raise ValueError(f"sample_topk_topp: uncond {tuple(uncond.shape)} / {uncond.stride()} must share cond's "
+                             f"shape and strides {tuple(cond.shape)} / {cond.stride()}")
+    lds = []
+    for t, nm in ((q, "q"), (x_out, "x_out")):
+        if t is None:
+            lds.append(0)
+            continue
+        _dev(t, f"sample_topk_topp({nm})", torch.float32, contiguous=False)
+        if t.is_contiguous() and t.numel() == R * V and t.shape[-1] == V:
+            lds.append(V)
+        elif tuple(t.shape) == (R, V) and t.stride(1) == 1:
+            lds.append(t.stride(0) if R > 1 else V)
+        else:
+            raise ValueError(f"sample_topk_topp: {nm} {tuple(t.shape)} / {t.stride()} vs {R} rows of {V}")
+    idx = torch.empty(cond.shape[:-1], dtype=torch.int64, device=cond.device)
+    e0 = OpTimer.begin()
+    _lib.call("eggroll_sample_topk_topp", cond.data_ptr(), _p(uncond), int(cond.dtype == torch.bfloat16), ld, rpb,
+              block_ld, float(w_cond), float(w_uncond), R, V, max(int(top_k), 0),
+              float(1 - top_p) if top_p > 0 else -1.0, q.data_ptr(), lds[0], idx.data_ptr(), _p(x_out), lds[1],
+              _stream(cond.device))
+    OpTimer.end(e0, "sample_topk_topp", float(R * V) * (cond.element_size() * (2 if uncond is not None else 1) + 4
+                                                         + (4 if x_out is not None else 0)), f"rows{R}")
+    return idx
+
+
 def gated_residual_(x: torch.Tensor, y: torch.Tensor, gate: torch.Tensor, rows_per_group: int) -> torch.Tensor:
     """x += gate[g] * y in place (g = row // rows_per_group); gate a [groups, C] view."""
     _dev(x, "gated_residual(x)", torch.bfloat16)

@@ -24,7 +24,9 @@ What is different from the reference, by design:
     stays fp32 as in the reference; the VQVAE decoder runs bf16 channels-last convolutions;
   * sampling: each member keeps its own device Generator seeded with g_seed (the reference seeds
     `self.rng` once per member's generate call, var.py:143-144), so member k's multinomial draws
-    consume exactly the stream the reference's k-th generate call would.
+    consume exactly the stream the reference's k-th generate call would; on the native sampler path
+    (`VARPopulationInfer.native_sampler`) the CFG combine, top-k / top-p and the draw of all members are one
+    eggroll_sample_topk_topp launch per scale on Exponential(1) draws filled from those same generators.
 State-dict keys are the reference's (`var_d16.pth` / `vae_ch160v4096z32.pth` load with
 `load_reference_state`), so a real checkpoint drops in; without one, weights are synthetic.
 """
@@ -458,6 +460,28 @@ def sample_population(logits: torch.Tensor, gens: Sequence[torch.Generator], top
                         for k in range(n)])
 
 
+BAD_PROBS = "probability tensor contains either inf, nan or element < 0"    # torch.multinomial's message
+
+
+def sample_population_native(head_out: torch.Tensor, t: float, gens: Sequence[torch.Generator], top_k: int,
+                             top_p: float, keep_logits: bool = False):
+    """head_out [n, 2, B, l, V] (the head GEMM's output, cond | uncond per member, bf16 or fp32) -> idx [n, B, l] and
+    the CFG logits [n, B, l, V] fp32 (None unless keep_logits): eggroll_sample_topk_topp, one launch for all members.
+    q[k] is filled from gens[k] as torch.multinomial fills its own (`empty_like(probs).exponential_(1, gen)` over the
+    member's [B*l, V] probabilities), so every generator advances exactly as under `sample_population`.  A row with
+    NaN / +inf logits comes back as -1 (torch.multinomial raises there; the caller decides when to look)."""
+    n, two, B, l, V = head_out.shape
+    if two != 2 or len(gens) != n or not head_out.is_contiguous():
+        raise ValueError(f"sample_population_native: head_out {tuple(head_out.shape)} vs {len(gens)} generators")
+    q = torch.empty((n, B * l, V), dtype=torch.float32, device=head_out.device)
+    for k in range(n):
+        q[k].exponential_(1, generator=gens[k])
+    x_out = torch.empty((n, B, l, V), dtype=torch.float32, device=head_out.device) if keep_logits else None
+    ho = head_out.view(n, 2, B * l, V)
+    idx = K.sample_topk_topp(ho[:, 0], q, top_k, top_p, uncond=ho[:, 1], w_cond=1 + t, w_uncond=t, x_out=x_out)
+    return idx.view(n, B, l), x_out
+
+
 # ---------------------------------------------------------------------------------------
 # population autoregressive inference
 # ---------------------------------------------------------------------------------------
@@ -466,8 +490,11 @@ def sample_population(logits: torch.Tensor, gens: Sequence[torch.Generator], top
 class VARPopulationInfer:
     """var.py:126-190 `autoregressive_infer_cfg` for n members at once (more_smooth=False)."""
 
-    def __init__(self, var: VARTransformer, vae: VQVAEDecode, use_kernel: bool = True):
+    def __init__(self, var: VARTransformer, vae: VQVAEDecode, use_kernel: bool = True, native_sampler: bool = True):
         self.var, self.vae = var, vae
+        # eggroll_sample_topk_topp: CFG combine, top-k / top-p and the draw in one launch per scale (False, forced
+        # tokens or CPU tensors: `sample_population`, the torch op chain with one multinomial per member)
+        self.native_sampler = native_sampler
         # eggroll_qk_l2norm_kv + eggroll_flash_attention at head dim 64, GELU / gated residuals as GEMM epilogues
         # (False: the torch forms, F.normalize + SDPA over a head-major cache: A/B, tests)
         self.use_kernel = use_kernel
@@ -523,6 +550,7 @@ class VARPopulationInfer:
         f_hat = torch.zeros((n * B, a.Cvae, a.patch_nums[-1], a.patch_nums[-1]), dtype=torch.float32, device=dev)
         code = self.vae.quantize.embedding.weight.float()
         idx_all, logits_all = [], []
+        bad = None          # native sampler: device flag, some row of some scale had NaN / +inf logits (token -1)
         cur = 0
         for si, pn in enumerate(a.patch_nums):
             l = pn * pn
@@ -547,15 +575,26 @@ class VARPopulationInfer:
                 K.gated_residual_(x, f, ada[:, C:2 * C], rows_per_group=l)
             cur += l
             h = K.rownorm(x, a.norm_eps, layer=True, mscale=ada_h[:, 0:C], mshift=ada_h[:, C:2 * C], rows_per_group=l)
-            logits = var.head(h).float().view(n, 2, B, l, a.vocab_size)
+            head_out = var.head(h)
             t = cfg * ratio
-            logits = (1 + t) * logits[:, 0] - t * logits[:, 1]                                       # [n, B, l, V]
-            if keep_logits:
-                logits_all.append(logits.clone())
-            if force_idx is not None:
-                idx = force_idx[si].to(dev).view(n, B, l)
+            if self.native_sampler and force_idx is None and head_out.is_cuda:
+                # CFG combine, top-k / top-p and the draw in one launch off the head GEMM's bf16 output
+                idx, logits = sample_population_native(head_out.view(n, 2, B, l, a.vocab_size), t, gens, top_k, top_p,
+                                                       keep_logits)
+                if keep_logits:
+                    logits_all.append(logits)
+                neg = (idx < 0).any()
+                bad = neg if bad is None else bad | neg
+                idx = idx.clamp_(min=0)
             else:
-                idx = sample_population(logits, gens, top_k, top_p)
+                logits = head_out.float().view(n, 2, B, l, a.vocab_size)
+                logits = (1 + t) * logits[:, 0] - t * logits[:, 1]                                   # [n, B, l, V]
+                if keep_logits:
+                    logits_all.append(logits.clone())
+                if force_idx is not None:
+                    idx = force_idx[si].to(dev).view(n, B, l)
+                else:
+                    idx = sample_population(logits, gens, top_k, top_p)
             idx_all.append(idx.reshape(n * B, l))
             h_BChw = code[idx.reshape(n * B, l)].transpose(1, 2).reshape(n * B, a.Cvae, pn, pn)
             f_hat, nxt = self.vae.next_autoregressive_input(si, SN, f_hat, h_BChw)
@@ -564,6 +603,8 @@ class VARPopulationInfer:
                 nxt = F.linear(nxt.reshape(n * B, a.Cvae, -1).transpose(1, 2), var.word_embed.weight.float(),
                                var.word_embed.bias.float()) + lvl_pos[cur:cur + ln]                 # [nB, l', C]
                 x = nxt.view(n, 1, B, ln, C).expand(n, 2, B, ln, C).to(torch.bfloat16).reshape(-1, C).contiguous()
+        if bad is not None and bool(bad):       # the generation's one sync (torch.multinomial's check: one per call)
+            raise RuntimeError(BAD_PROBS)
         return f_hat, idx_all, logits_all
 
 
@@ -579,7 +620,8 @@ class VARClassGenerator:
 
     def __init__(self, model_depth: int = 16, device: str = "cuda:0", DTYPE: torch.dtype = torch.float16,
                  arch: Optional[VARArch] = None, num_classes: int = 1000, weight_seed: int = 0,
-                 vae_chunk: int = 16, native_attention: bool = True, native_vae_conv: bool = True):
+                 vae_chunk: int = 16, native_attention: bool = True, native_vae_conv: bool = True,
+                 native_sampler: bool = True):
         if arch is None:
             if model_depth not in {16, 20, 24, 30}:
                 raise ValueError("model_depth must be one of {16, 20, 24, 30}")
@@ -599,7 +641,7 @@ class VARClassGenerator:
         self.transformer = self.var
         self.vae_chunk = vae_chunk
         self.ctx = PopulationContext()
-        self.infer = VARPopulationInfer(self.var, self.vae, use_kernel=native_attention)
+        self.infer = VARPopulationInfer(self.var, self.vae, use_kernel=native_attention, native_sampler=native_sampler)
 
     def _cast(self):
         """Frozen transformer linears bf16 (MFMA operands); VQVAE decoder bf16 channels-last."""

@@ -612,6 +612,36 @@ int eggroll_qk_norm_rope_half(void* x, int64_t ldx, int64_t B, int64_t N, int64_
 int eggroll_gguf_dequant(int32_t ggml_type, const void* blocks, int64_t n_elems, void* out, int32_t out_fp32,
                          void* stream);
 
+/* Top-k / top-p token sampling of R rows of V logits, one token per row, one launch (VAR's
+ * sample_with_top_k_top_p_ with num_samples = 1, VAR_models/helpers.py:6-19, restated; the classifier-free-guidance
+ * combine of VAR_models/var.py:171-172 in front of it).  Row r of cond starts at element
+ *   (r / rows_per_block) * block_ld + (r % rows_per_block) * ld
+ * and uncond follows the same rule (a head output [n, 2, rows, V]: uncond = cond + rows * V, block_ld = 2 rows V,
+ * rows_per_block = rows).  bf16 (in_bf16 == 1) or fp32 (0) inputs; uncond == NULL: no combine, the weights are
+ * ignored.  Per row, all in fp32:
+ *   1. x_j = fl(fl(w_cond c_j) - fl(w_uncond u_j)): two products rounded on their own, no FMA (torch's
+ *      (1 + t) * c - t * u with w_cond = float(1 + t), w_uncond = float(t), bit for bit); written to
+ *      x_out[r * ldx + j] when x_out is given, before any masking.
+ *   2. 0 < top_k < V: entries below the top_k-th largest x (counted with multiplicity) are masked; ties at it stay.
+ *   3. p_cut >= 0 (= float(1 - top_p); negative: off): with p the softmax over the unmasked entries and
+ *      C(v) = sum of p_i over unmasked i with x_i <= v, entry j is masked when C(x_j) <= p_cut and x_j is below
+ *      the row maximum.  Equal logits are kept or dropped together (torch's unstable sort decides inside a tie
+ *      group; this definition does not depend on one).
+ *   4. idx[r] = the lowest index of argmax_j p'_j / q[r * ldq + j], p' the softmax over what is left and q the
+ *      caller's Exponential(1) draws (what torch.multinomial draws for itself), p'_j / q_j as two fp32 divisions.
+ *   5. a row whose x holds NaN or +inf, or nothing finite, gets idx[r] = -1 and nothing else is written for it
+ *      (its x_out row included); inputs of -inf are ordinary masked entries.
+ * A row's result depends on that row alone (one workgroup per row, fixed reduction order, no atomics): the same in
+ * every launch and in every batch.
+ * Class: V a multiple of 4 in [2, 4096]; ld, ldq, ldx >= V; ld, block_ld, ldq, ldx multiples of 4; block_ld >= 0;
+ * rows_per_block >= 1; 0 <= R < 2^31; top_k >= 0; p_cut not NaN; cond / uncond 8-byte (bf16) or 16-byte (fp32)
+ * aligned, q / x_out 16-byte, idx 8-byte.  Anything else returns -1 with eggroll_last_error() naming
+ * "sample_topk_topp" and writes nothing.  R == 0 is a no-op returning 0. */
+int eggroll_sample_topk_topp(const void* cond, const void* uncond, int32_t in_bf16, int64_t ld, int64_t rows_per_block,
+                             int64_t block_ld, float w_cond, float w_uncond, int64_t R, int64_t V, int32_t top_k,
+                             float p_cut, const float* q, int64_t ldq, int64_t* idx, float* x_out, int64_t ldx,
+                             void* stream);
+
 #ifdef __cplusplus
 }
 #endif
