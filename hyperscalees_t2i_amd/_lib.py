@@ -108,6 +108,8 @@ SIGNATURES = {
     "eggroll_gguf_dequant": (C.c_int, [i32, vp, i64, vp, i32, vp]),
     "eggroll_sample_topk_topp": (C.c_int, [vp, vp, i32, i64, i64, i64, f32, f32, i64, i64, i32, f32, vp, i64, vp, vp,
                                            i64, vp]),
+    "eggroll_sample_bits": (C.c_int, [vp, i32, i64, i64, i64, i64, i64, i64, f32, f32, f32, i32, f32, vp, vp, vp, i32,
+                                      f32, vp, vp, vp]),
 }
 
 _lib = None

@@ -704,6 +704,7 @@ class InfinityConfig:
     weight_seed: int = 0
     synthetic_weights: bool = False          # no Infinity checkpoint loader: True is required (explicit opt-in)
     native_vae_conv: bool = True             # the VAE's 160 / 320 / 640-wide 3x3 convs on eggroll_conv_nhwc (False: MIOpen)
+    native_sampler: bool = True              # eggroll_sample_bits, one launch per scale (False: torch ops + multinomial per chunk and member)
 
 
 def synthetic_infinity_prompt_data(P: int = 4, lens: Tuple[int, int] = (16, 100), dim: int = 2048,
@@ -777,7 +778,7 @@ class InfinityBackend(ESBackend):
                                    sampling_per_bits=int(c.sampling_per_bits), device=self.device,
                                    synthetic_weights=c.synthetic_weights, arch=c.arch, weight_seed=c.weight_seed,
                                    vae_chunk=c.vae_chunk, kv_budget_gb=c.kv_budget_gb,
-                                   native_vae_conv=c.native_vae_conv)
+                                   native_vae_conv=c.native_vae_conv, native_sampler=c.native_sampler)
         n = attach_lora(self.es_model.transformer, c.lora_r, c.lora_alpha, c.lora_target_modules)
         if n == 0:
             raise RuntimeError("no LoRA target module matched")

@@ -22,7 +22,9 @@ residual add into their epilogues); q / k L2 norm + 2-D RoPE in one in-place pas
 the whole schedule, read in place) on eggroll_flash_attention; everything text-side (member-independent: no LoRA there) computed once per distinct
 prompt.  The reference's generator semantics are kept per micro-batch (es_backend.py:951-1022: every
 micro-batch call reseeds with the same seed), so member k's bits equal those of the reference's own
-per-member calls given the same logits.
+per-member calls given the same logits; on the native sampler path (`InfinityPopulationInfer.native_sampler`)
+the per-scale tail from the head GEMM's output to the bits and their BSQ codes is one eggroll_sample_bits
+launch for all members, on Exponential(1) draws filled once per chunk from that same generator stream.
 """
 from __future__ import annotations
 
@@ -38,7 +40,7 @@ from . import kernels as K
 from .flux_vae import FluxVAEDecoder
 from .lora import LoRALinear
 from .sana import attach_lora
-from .var import top_k_top_p_mask_
+from .var import BAD_PROBS, top_k_top_p_mask_
 
 INFINITY_LORA_TARGETS = ["fc1"]   # unifed_es.py:472
 
@@ -334,11 +336,40 @@ class ChunkedBitSampler:
         return bits
 
 
+class ChunkedBitDraws:
+    """ChunkedBitSampler's generator streams without its sampling: the Exponential(1) draws `torch.multinomial` would
+    make for itself in each chunk call, filled once per chunk instead of once per (chunk, member): every member's
+    chunk call starts from the same state, so all members draw the same numbers.  q[c0:c1] is contiguous and has the
+    element count of the [mb * l * d, 2] probabilities a chunk call draws over, so the generator advances exactly as
+    under `sample_bits`, and states[c0] after a scale equals ChunkedBitSampler's."""
+
+    def __init__(self, gen: torch.Generator, B: int, mb: int):
+        self.gen, self.B, self.mb = gen, int(B), int(mb)
+        st = gen.get_state()
+        self.states = {c0: st for c0 in range(0, self.B, self.mb)}
+
+    def fill(self, q: torch.Tensor) -> torch.Tensor:
+        """q [B, l*d, 2] fp32, contiguous, on the generator's device: filled in place and returned."""
+        if q.shape[0] != self.B or q.shape[-1] != 2 or not q.is_contiguous() or q.dtype != torch.float32:
+            raise ValueError(f"ChunkedBitDraws.fill: q {tuple(q.shape)} {q.dtype} is no contiguous fp32 "
+                             f"[{self.B}, l*d, 2]")
+        for c0, pre in self.states.items():
+            c1 = min(self.B, c0 + self.mb)
+            self.gen.set_state(pre)
+            q[c0:c1].view(-1, 2).exponential_(1, generator=self.gen)
+            self.states[c0] = self.gen.get_state()
+        return q
+
+
 class InfinityPopulationInfer:
     """`autoregressive_infer_cfg` (models/Infinity.py:509-537) for n members at once."""
 
-    def __init__(self, tr: InfinityTransformer, vae: FluxVAEDecoder):
+    def __init__(self, tr: InfinityTransformer, vae: FluxVAEDecoder, native_sampler: bool = True):
         self.tr, self.vae = tr, vae
+        # eggroll_sample_bits: tau, the CFG combine, top-k / top-p, the draw and the BSQ codes in one launch per scale
+        # on one ChunkedBitDraws fill (False, forced bits or CPU tensors: the torch op chain with one
+        # `sample_bits` call per chunk and member)
+        self.native_sampler = native_sampler
         self.use_kernel = True    # eggroll_qk_norm_rope + eggroll_flash_attention at head dim 128 (False: torch forms)
 
     # ---- text side (member-independent) ------------------------------------------------
@@ -479,7 +510,10 @@ class InfinityPopulationInfer:
         x = (sos[drow] + tr.pos_start.float().view(1, C)).to(torch.bfloat16).contiguous()   # [N2 * 1, C]
         summed = torch.zeros((n * B, a.codebook_dim, vside, vside), dtype=torch.float32, device=dev)
         mb = B if micro_batch <= 0 or micro_batch >= B else int(micro_batch)
-        sampler = ChunkedBitSampler(torch.Generator(device=dev).manual_seed(int(g_seed)), B, mb)
+        native = self.native_sampler and force_bits is None and dev.type == "cuda"
+        gen = torch.Generator(device=dev).manual_seed(int(g_seed))
+        sampler = ChunkedBitDraws(gen, B, mb) if native else ChunkedBitSampler(gen, B, mb)
+        bad = torch.zeros(1, dtype=torch.int32, device=dev) if native else None
         bits_all, logits_all = [], []
         cur = 0
         for si, (_, h, w) in enumerate(schedule):
@@ -493,18 +527,28 @@ class InfinityPopulationInfer:
                 self._block(blk, x, l, cur, caches[bi], m32, m16, cas[bi][0], cas[bi][1], cabias, cos, sin)
             cur += l
             hn = K.rownorm(x, a.norm_eps, layer=True, mscale=ada_h[:, :C], mshift=ada_h[:, C:], rows_per_group=l)
-            lg = tr.head(hn).float().view(n, 2, B, l * a.d_tok, 2) / float(tau_list[si])
             cfg = float(cfg_list[si])
-            lg = cfg * lg[:, 0] + (1.0 - cfg) * lg[:, 1]                                   # [n, B, l*d, 2]
-            if keep_logits:
-                logits_all.append(lg.clone())
-            if force_bits is not None:
-                bits = force_bits[si].to(dev).view(n, B, l * a.d_tok).long()
+            if native:
+                # tau, the CFG combine, top-k / top-p, the draw and bits_to_codes: one launch off the head GEMM's output
+                q = sampler.fill(torch.empty((B, l * a.d_tok, 2), dtype=torch.float32, device=dev))
+                lg = torch.empty((n, B, l * a.d_tok, 2), dtype=torch.float32, device=dev) if keep_logits else None
+                bits, codes = K.sample_bits(tr.head(hn), q, n, B, h, w, a.d_tok, float(tau_list[si]), cfg, top_k, top_p,
+                                            bool(a.spatial_patchify), bad, x_out=lg)
+                if keep_logits:
+                    logits_all.append(lg)
+                bits_all.append(bits)
             else:
-                bits = sampler.sample(lg, top_k, top_p)
-            bits = bits.view(n * B, l, a.d_tok)
-            bits_all.append(bits)
-            codes = bits_to_codes(bits, a, h, w)
+                lg = tr.head(hn).float().view(n, 2, B, l * a.d_tok, 2) / float(tau_list[si])
+                lg = cfg * lg[:, 0] + (1.0 - cfg) * lg[:, 1]                               # [n, B, l*d, 2]
+                if keep_logits:
+                    logits_all.append(lg.clone())
+                if force_bits is not None:
+                    bits = force_bits[si].to(dev).view(n, B, l * a.d_tok).long()
+                else:
+                    bits = sampler.sample(lg, top_k, top_p)
+                bits = bits.view(n * B, l, a.d_tok)
+                bits_all.append(bits)
+                codes = bits_to_codes(bits, a, h, w)
             if si != len(schedule) - 1:
                 summed.add_(F.interpolate(codes, size=(vside, vside), mode="bilinear", align_corners=False))
                 _, h2, w2 = schedule[si + 1]
@@ -515,6 +559,8 @@ class InfinityPopulationInfer:
                 x = x.contiguous()
             else:
                 summed.add_(codes)
+        if bad is not None and bool(bad):       # the generation's one sync (torch.multinomial's check: one per call)
+            raise RuntimeError(BAD_PROBS)
         return summed, bits_all, logits_all
 
 

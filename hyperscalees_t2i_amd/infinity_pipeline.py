@@ -148,7 +148,7 @@ class InfinityES:
                  device: str = "cuda:0", DTYPE: torch.dtype = torch.bfloat16, sigma_data: float = 0.5,
                  # build knobs
                  synthetic_weights: bool = False, arch=None, weight_seed: int = 0, vae_chunk: int = 16,
-                 kv_budget_gb: float = 120.0, native_vae_conv: bool = True):
+                 kv_budget_gb: float = 120.0, native_vae_conv: bool = True, native_sampler: bool = True):
         os.environ["TOKENIZERS_PARALLELISM"] = "false"
         self.device, self.DTYPE, self.bf16 = device, torch.bfloat16, bool(bf16)
         if float(h_div_w_template) != 1.0:
@@ -191,6 +191,8 @@ class InfinityES:
         self.vae_chunk = int(vae_chunk)
         self.kv_budget = float(kv_budget_gb) * 2 ** 30
         self.ctx = PopulationContext()
+        # eggroll_sample_bits, one launch per scale (False: the torch op chain, one sample_bits call per chunk and member)
+        self.native_sampler = bool(native_sampler)
 
     # ---- prompt cache (models/Infinity.py:257-349) ---------------------------------------
     def encode_prompts(self, prompts_txt_path, encoded_save_path, batch_size: int = 8, complex_human_instruction=None,
@@ -265,7 +267,7 @@ class InfinityES:
         T = len(self.scale_schedule)
         cfg = as_schedule_list(cfg_list, "cfg_list", T)
         tau = as_schedule_list(tau_list, "tau_list", T)
-        inf = InfinityPopulationInfer(self.transformer, self.vae)
+        inf = InfinityPopulationInfer(self.transformer, self.vae, native_sampler=self.native_sampler)
         B = int(idx.numel())
         per = self.members_per_pass(n, B) if theta_pop is not None else 1
         imgs, extras = [], []

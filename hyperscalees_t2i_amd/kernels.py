@@ -838,6 +838,61 @@ def sample_topk_topp(cond: torch.Tensor, q: torch.Tensor, top_k: int = 0, top_p:
     return idx
 
 
+def inv_tau_of(tau: float) -> float:
+    """The fp32 factor torch multiplies by on the GPU for `tensor / tau` with a host scalar tau (a division by a
+    host scalar is a multiplication by its reciprocal there): float32(1.0 / tau), the reciprocal taken in double."""
+    return float(np.float32(1.0 / float(tau)))
+
+
+def sample_bits(head: torch.Tensor, q: torch.Tensor, n: int, B: int, h: int, w: int, d_tok: int, tau: float, cfg: float,
+                top_k: int, top_p: float, patchify: bool, bad: torch.Tensor,
+                x_out: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """eggroll_sample_bits: Infinity's bits and BSQ codes of one scale, all members in one launch.  head: the head
+    GEMM's output [n * 2 * B * h * w, >= 2 * d_tok] bf16 / fp32 with unit inner stride, rows
+    [member][cond | uncond][image][token], columns [bit][class], read in place.  The logits sampled are
+    x = cfg * (head_cond / tau) + (1.0 - cfg) * (head_uncond / tau) as torch computes them on the GPU (the division a
+    multiplication by the fp32 reciprocal).  top_k 0 or >= 2: no top-k; top_p <= 0: no top-p.  q: fp32 contiguous
+    [B, h * w * d_tok, 2] Exponential(1) draws shared by all members; bad: int32 [1], set to 1 when any bit's x holds
+    NaN / +inf or two -inf (never cleared here); x_out (optional, fp32 contiguous [n, B, h * w * d_tok, 2]) receives
+    x.  Returns bits int64 [n * B, h * w, d_tok] (-1 at a bad bit) and codes fp32 [n * B, codebook_dim, H', W']
+    (== infinity.bits_to_codes(bits); 0 at a bad bit), codebook_dim = d_tok / 4 and H' x W' = 2h x 2w with patchify."""
+    _dev(head, "sample_bits(head)", contiguous=False)
+    if head.dtype not in (torch.bfloat16, torch.float32):
+        raise _lib.EggrollError(f"sample_bits(head): expected bf16 or fp32, got {head.dtype}")
+    n, B, h, w, d_tok = int(n), int(B), int(h), int(w), int(d_tok)
+    L = h * w
+    rows = n * 2 * B * L
+    if head.dim() != 2 or head.shape[0] != rows or head.shape[1] < 2 * d_tok or head.stride(1) != 1:
+        raise ValueError(f"sample_bits: head {tuple(head.shape)} / {head.stride()} is no [{rows}, >= {2 * d_tok}] view "
+                         "with unit inner stride")
+    ld = head.stride(0) if rows > 1 else head.shape[1]
+    if patchify and d_tok % 4:
+        raise ValueError(f"sample_bits: d_tok={d_tok} must be a multiple of 4 with patchify")
+    _dev(q, "sample_bits(q)", torch.float32)
+    if tuple(q.shape) != (B, L * d_tok, 2):
+        raise ValueError(f"sample_bits: q {tuple(q.shape)} vs {(B, L * d_tok, 2)}")
+    _dev(bad, "sample_bits(bad)", torch.int32)
+    if bad.numel() != 1:
+        raise ValueError(f"sample_bits: bad {tuple(bad.shape)} must hold one int32")
+    if x_out is not None:
+        _dev(x_out, "sample_bits(x_out)", torch.float32)
+        if tuple(x_out.shape) != (n, B, L * d_tok, 2):
+            raise ValueError(f"sample_bits: x_out {tuple(x_out.shape)} vs {(n, B, L * d_tok, 2)}")
+    cd, up = (d_tok // 4, 2) if patchify else (d_tok, 1)
+    bits = torch.empty((n * B, L, d_tok), dtype=torch.int64, device=head.device)
+    codes = torch.empty((n * B, cd, h * up, w * up), dtype=torch.float32, device=head.device)
+    e0 = OpTimer.begin()
+    _lib.call("eggroll_sample_bits", head.data_ptr(), int(head.dtype == torch.bfloat16), ld, n, B, h, w, d_tok,
+              inv_tau_of(tau),
+              float(cfg), float(1.0 - cfg), max(int(top_k), 0), float(np.float32(1 - top_p)) if top_p > 0 else -1.0,
+              q.data_ptr(), bits.data_ptr(), codes.data_ptr(), int(bool(patchify)), float(1.0 / math.sqrt(cd)),
+              _p(x_out), bad.data_ptr(), _stream(head.device))
+    nbits = float(n * B * L * d_tok)
+    OpTimer.end(e0, "sample_bits", nbits * (4 * head.element_size() + 8 + 8 + 4 + (8 if x_out is not None else 0)),
+                f"bits{int(nbits)}")
+    return bits, codes
+
+
 def gated_residual_(x: torch.Tensor, y: torch.Tensor, gate: torch.Tensor, rows_per_group: int) -> torch.Tensor:
     """x += gate[g] * y in place (g = row // rows_per_group); gate a [groups, C] view."""
     _dev(x, "gated_residual(x)", torch.bfloat16)

@@ -642,6 +642,45 @@ int eggroll_sample_topk_topp(const void* cond, const void* uncond, int32_t in_bf
                              float p_cut, const float* q, int64_t ldq, int64_t* idx, float* x_out, int64_t ldx,
                              void* stream);
 
+/* Infinity's bit sampling of one scale, all members in one launch: the per-scale tail of `autoregressive_infer_cfg`
+ * (tau, the classifier-free-guidance combine, sample_with_top_k_top_p_ over the two classes of a bit with
+ * num_samples = 1, and the BSQ codes of the drawn bits) restated.  L = h * w tokens of d_tok bits per image.
+ * head: the head GEMM's output read in place, bf16 (in_bf16 == 1) or fp32 (0), row stride ld elements.  Row
+ *   ((k * 2 + half) * B + j) * L + t  holds member k < n, cond (half = 0) or uncond (half = 1), image j < B, token t;
+ * columns 2 i + c hold bit i < d_tok, class c in {0, 1}.  q: fp32 [B][L * d_tok][2], the caller's Exponential(1) draws
+ * (what torch.multinomial draws for itself), shared by all members.  Per bit, all in fp32, every operation rounded on
+ * its own (no FMA):
+ *   1. x_c = fl(fl(w_cond fl(cond_c inv_tau)) + fl(w_uncond fl(uncond_c inv_tau))): bit for bit torch's
+ *      `lg = head.float() / tau; cfg * lg[:, 0] + (1.0 - cfg) * lg[:, 1]` on the GPU with
+ *      inv_tau = float(1.0 / tau), w_cond = float(cfg), w_uncond = float(1.0 - cfg), each taken in double and then
+ *      rounded.  torch divides a tensor by a host scalar on the GPU as a multiplication by that reciprocal (measured
+ *      on MI355X at tau = 0.7 and 1.7, where 1.0f / float(tau) is one ulp off; the CPU divides), so the entry takes
+ *      the factor, not tau.  Written to x_out[k][j][t * d_tok + i][c] (fp32 [n][B][L * d_tok][2]) when x_out is
+ *      given, before any masking.
+ *   2. top_k == 1 masks the smaller of the two; top_k == 0 or >= 2 masks nothing.  Equal values both stay.
+ *   3. p_cut >= 0 (= float(1 - top_p); negative: off): with lo < hi the two logits and
+ *      p_lo = e^(lo - hi) / (1 + e^(lo - hi)), the smaller entry is masked when p_lo <= p_cut.  Equal logits are kept
+ *      together (torch's unstable sort decides inside a tie; this definition does not depend on one).
+ *   4. bits = the lowest index of argmax_c p'_c / q_c, p' the softmax over what is left (0 for a masked entry),
+ *      p'_c / q_c as two fp32 divisions.
+ *   5. a bit whose x holds NaN or +inf, or two -inf, gets bits = -1, codes = 0 and *bad = 1 (a plain store of the
+ *      constant; the caller zeroes it and looks when it likes), and nothing else is written for it (its x_out pair
+ *      included).  A single -inf is an ordinary masked entry.
+ * bits: int64 [n * B][L][d_tok].  codes: fp32 [n * B][codebook_dim][H'][W'], value +code_mag for a 1 and -code_mag
+ * for a 0 (code_mag = float(1 / sqrt(codebook_dim))): bit i of token (y, x) is channel i of pixel (y, x) when
+ * patchify == 0 (codebook_dim = d_tok, H' x W' = h x w), channel i / 4 of pixel (2 y + (i / 2) % 2, 2 x + i % 2) when
+ * patchify == 1 (codebook_dim = d_tok / 4, 2 h x 2 w: pixel_shuffle by 2).
+ * A bit's result depends on that bit's inputs alone (no atomics, no cross-workgroup traffic): the same in every launch
+ * and for every n.
+ * Class: d_tok >= 1; patchify 0 or 1 and d_tok % 4 == 0 with 1; ld even and >= 2 d_tok; n, B, h, w >= 0 and
+ * n B h w d_tok < 2^31; top_k >= 0; p_cut not NaN; head, codes, x_out, bad 4-byte aligned, q and bits 8-byte.
+ * Anything else, or a null head / q / bits / codes / bad with work to do, returns -1 with eggroll_last_error() naming
+ * "sample_bits" and writes nothing.  Zero work (any of n, B, h, w zero) is a no-op returning 0. */
+int eggroll_sample_bits(const void* head, int32_t in_bf16, int64_t ld, int64_t n, int64_t B, int64_t h, int64_t w,
+                        int64_t d_tok, float inv_tau, float w_cond, float w_uncond, int32_t top_k, float p_cut,
+                        const float* q, int64_t* bits, float* codes, int32_t patchify, float code_mag, float* x_out,
+                        int32_t* bad, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
