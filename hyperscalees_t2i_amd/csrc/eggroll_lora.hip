@@ -258,16 +258,13 @@ __global__ __launch_bounds__(256) void k_lora_project_mfma(const unsigned short*
 }
 
 // ------------------------------------------------------------------------------------
-// Base GEMM + fused LoRA epilogue, templated on the tile:
-//   Tile<BM, BN, WM, WN>: BM x BN output tile, BK = 64, WM x WN waves (wave tile (BM/WM) x (BN/WN)),
-//   2 LDS stages of (BM + BN) rows x 128 B, one barrier per K-tile: the global_load_lds of K-tile
-//   k+1 is issued right after the barrier and lands while the MFMAs of K-tile k run.
-//   kT128: 128x128, 4 waves (2 blocks/CU, 64 KiB LDS).  kT256: 256x256, 8 waves (1 block/CU,
-//   128 KiB LDS) — half the LDS bytes per FLOP.
+// Base GEMM + fused LoRA epilogue on the one-barrier tile (kernel 128):
+//   BM x BN = 128 x 128 output tile, BK = 64, WM x WN = 2 x 2 waves (wave tile 64 x 64), 2 LDS stages
+//   of (BM + BN) rows x 128 B (64 KiB, 2 blocks/CU), one barrier per K-tile: the global_load_lds of
+//   K-tile k+1 is issued right after the barrier and lands while the MFMAs of K-tile k run.
 // ------------------------------------------------------------------------------------
-template <int BM_, int BN_, int WM_, int WN_>
-struct Tile {
-    static constexpr int BM = BM_, BN = BN_, WM = WM_, WN = WN_;
+struct T128 {
+    static constexpr int BM = 128, BN = 128, WM = 2, WN = 2;
     static constexpr int WAVES = WM * WN, THREADS = 64 * WAVES;
     static constexpr int WTM = BM / WM, WTN = BN / WN;   // wave tile
     static constexpr int FM = WTM / 16, FN = WTN / 16;   // 16x16 fragments per wave
@@ -275,12 +272,9 @@ struct Tile {
     static constexpr int STAGE = A_BYTES + B_BYTES;
     static constexpr int LDS = 2 * STAGE;
     static constexpr int GA = BM / 8 / WAVES, GB = BN / 8 / WAVES;   // glds per wave per K-tile
-    static constexpr int MIN_BLOCKS = (LDS <= 80 * 1024) ? 2 : 1;
     static_assert(BM % (8 * WAVES) == 0 && BN % (8 * WAVES) == 0, "staging split");
     static_assert(WTM * WTN * 2 <= LDS / WAVES, "epilogue staging must fit");
 };
-using kT128 = Tile<128, 128, 2, 2>;
-using kT256 = Tile<256, 256, 2, 4>;
 
 // Stage `nglds` x 8 rows of a K-contiguous bf16 matrix into an LDS tile.  LDS image: row r at
 // byte 128*r; 16-B slot s' of row r holds global chunk s' ^ (r & 7)  (conflict-free b128
@@ -304,186 +298,10 @@ __device__ __forceinline__ bf16x8 read_frag(const char* lds_tile, int row, int c
     return *reinterpret_cast<const bf16x8*>(lds_tile + row * 128 + ((chunk ^ (row & 7)) << 4));
 }
 
-template <int R, class TL>
-__global__ __launch_bounds__(TL::THREADS, TL::MIN_BLOCKS) void k_lora_gemm(
-    const unsigned short* __restrict__ X, int64_t ldx, const unsigned short* __restrict__ W, int64_t ldw,
-    const unsigned short* __restrict__ bias, const float* __restrict__ T, const float* __restrict__ theta_pop,
-    int64_t ld_theta, int64_t offB, float scale, int rows_per_member, int M, int N, int64_t K, int tiles_n,
-    unsigned short* __restrict__ Y, int64_t ldy) {
-    constexpr int FM = TL::FM, FN = TL::FN;
-    __shared__ __attribute__((aligned(16))) char smem[TL::LDS];
-    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wm = wave / TL::WN, wn = wave % TL::WN;
-    const TileIdx ti = p8_tile_index<TL::BM>(M, tiles_n);
-    const int m0 = ti.m * TL::BM, n0 = ti.n * TL::BN;
-
-    f32x4 acc[FM][FN];
-#pragma unroll
-    for (int i = 0; i < FM; ++i)
-#pragma unroll
-        for (int j = 0; j < FN; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-    const int nk = (int)(K / BK);
-    stage_rows<TL::GA>(X, ldx, m0, M - 1, 0, smem, wave, lane);
-    stage_rows<TL::GB>(W, ldw, n0, N - 1, 0, smem + TL::A_BYTES, wave, lane);
-    __syncthreads();
-    for (int kt = 0; kt < nk; ++kt) {
-        const char* cur = smem + (kt & 1) * TL::STAGE;
-        if (kt + 1 < nk) {
-            char* nxt = smem + ((kt + 1) & 1) * TL::STAGE;
-            stage_rows<TL::GA>(X, ldx, m0, M - 1, (int64_t)(kt + 1) * BK, nxt, wave, lane);
-            stage_rows<TL::GB>(W, ldw, n0, N - 1, (int64_t)(kt + 1) * BK, nxt + TL::A_BYTES, wave, lane);
-        }
-#pragma unroll
-        for (int kk = 0; kk < (FM <= 4 ? 2 : 0); ++kk) {
-            const int ch = kk * 4 + (lane >> 4);
-            bf16x8 b[FN];
-#pragma unroll
-            for (int f = 0; f < FN; ++f) b[f] = read_frag(cur + TL::A_BYTES, wn * TL::WTN + f * 16 + (lane & 15), ch);
-            if constexpr (FM <= 4) {
-                bf16x8 a[FM];
-#pragma unroll
-                for (int f = 0; f < FM; ++f) a[f] = read_frag(cur, wm * TL::WTM + f * 16 + (lane & 15), ch);
-                __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-                for (int i = 0; i < FM; ++i)
-#pragma unroll
-                    for (int j = 0; j < FN; ++j)
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[i], b[j], acc[i][j], 0, 0, 0);
-                __builtin_amdgcn_s_setprio(0);
-            } else {
-                // large wave tile: handled below as one software-pipelined K-tile
-            }
-        }
-        if constexpr (FM > 4) {
-            // 8 steps per K-tile (2 k-substeps x 4 A-fragment pairs); the operands of step s+1
-            // are read from LDS before the 8 MFMAs of step s are issued, so LDS latency hides
-            // under MFMA work (counted lgkmcnt) instead of a full drain per fragment pair.
-            const char* bt = cur + TL::A_BYTES;
-            const int rA = wm * TL::WTM + (lane & 15), rB = wn * TL::WTN + (lane & 15);
-            const int ch0 = lane >> 4, ch1 = 4 + (lane >> 4);
-            bf16x8 b[FN], bn[FN], a0, a1, n0, n1;
-#pragma unroll
-            for (int f = 0; f < FN; ++f) b[f] = read_frag(bt, rB + f * 16, ch0);
-            a0 = read_frag(cur, rA, ch0);
-            a1 = read_frag(cur, rA + 16, ch0);
-#pragma unroll
-            for (int st = 0; st < 8; ++st) {
-                const int pair = st & 3;
-                if (st < 7) {
-                    const int np = (st + 1) & 3, nch = ((st + 1) >> 2) ? ch1 : ch0;
-                    if (np == 0) {
-#pragma unroll
-                        for (int f = 0; f < FN; ++f) bn[f] = read_frag(bt, rB + f * 16, nch);
-                    }
-                    n0 = read_frag(cur, rA + (2 * np) * 16, nch);
-                    n1 = read_frag(cur, rA + (2 * np + 1) * 16, nch);
-                }
-                __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-                for (int j = 0; j < FN; ++j)
-                    acc[2 * pair][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a0, b[j], acc[2 * pair][j], 0, 0, 0);
-#pragma unroll
-                for (int j = 0; j < FN; ++j)
-                    acc[2 * pair + 1][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a1, b[j], acc[2 * pair + 1][j], 0, 0, 0);
-                __builtin_amdgcn_s_setprio(0);
-                if (st < 7) {
-                    a0 = n0;
-                    a1 = n1;
-                    if (((st + 1) & 3) == 0) {
-#pragma unroll
-                        for (int f = 0; f < FN; ++f) b[f] = bn[f];
-                    }
-                }
-            }
-        }
-        __syncthreads();
-    }
-
-    // ---- epilogue: + bias[n] + scale * T[row,:] . B_k[n,:]  ->  bf16 via LDS, 16-B stores ----
-    const int col_l = lane & 15, rq = (lane >> 4) * 4;
-    float bv[FN];
-    int colv[FN];
-#pragma unroll
-    for (int j = 0; j < FN; ++j) {
-        const int col = n0 + wn * TL::WTN + j * 16 + col_l;
-        colv[j] = col < N ? col : N - 1;
-        bv[j] = bias ? bf16_to_f32(bias[colv[j]]) : 0.0f;
-    }
-    // stage this wave's WTM x WTN bf16 sub-tile in LDS (rows of WTN*2 bytes, 16-B slots XOR-swizzled);
-    // the LoRA term is added row by row so accumulators retire as they are written.
-    constexpr int ROWB = TL::WTN * 2, SLOTS = ROWB / 16;
-    char* ctile = smem + wave * (TL::WTM * ROWB);
-    float bk[FN][R > 0 ? R : 1];
-    bool one_member = true;
-    if constexpr (R > 0) {
-        const int first = m0 / rows_per_member;
-        const int last_row = (m0 + TL::BM - 1 < M ? m0 + TL::BM - 1 : M - 1);
-        one_member = (last_row / rows_per_member) == first;
-        const float* Bk = theta_pop + (int64_t)first * ld_theta + offB;
-#pragma unroll
-        for (int j = 0; j < FN; ++j)
-#pragma unroll
-            for (int qq = 0; qq < R; ++qq) bk[j][qq] = Bk[colv[j] * R + qq];
-    }
-#pragma unroll
-    for (int i = 0; i < FM; ++i) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const int rr = i * 16 + rq + e;
-            float add[FN];
-#pragma unroll
-            for (int j = 0; j < FN; ++j) add[j] = bv[j];
-            if constexpr (R > 0) {
-                int row = m0 + wm * TL::WTM + rr;
-                row = row < M ? row : M - 1;
-                float t[R];
-#pragma unroll
-                for (int qq = 0; qq < R; ++qq) t[qq] = T[(int64_t)row * R + qq];
-                if (!one_member) {
-                    const float* Bk = theta_pop + (int64_t)(row / rows_per_member) * ld_theta + offB;
-#pragma unroll
-                    for (int j = 0; j < FN; ++j)
-#pragma unroll
-                        for (int qq = 0; qq < R; ++qq) bk[j][qq] = Bk[colv[j] * R + qq];
-                }
-#pragma unroll
-                for (int j = 0; j < FN; ++j) {
-                    float d = 0.0f;
-#pragma unroll
-                    for (int qq = 0; qq < R; ++qq) d += t[qq] * bk[j][qq];
-                    add[j] += scale * d;
-                }
-            }
-#pragma unroll
-            for (int j = 0; j < FN; ++j) {
-                const int cc = j * 16 + col_l;
-                const int slot = (cc >> 3) ^ (rr & (SLOTS - 1));
-                *reinterpret_cast<unsigned short*>(ctile + rr * ROWB + slot * 16 + (cc & 7) * 2) =
-                    f32_to_bf16(acc[i][j][e] + add[j]);
-            }
-        }
-    }
-    __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0): this wave's LDS writes done (wave-private tile)
-    constexpr int ROWS_PER_IT = 64 / SLOTS;
-#pragma unroll
-    for (int it = 0; it < TL::WTM / ROWS_PER_IT; ++it) {
-        const int rr = it * ROWS_PER_IT + lane / SLOTS, sl = lane % SLOTS;
-        const int row = m0 + wm * TL::WTM + rr;
-        const int col = n0 + wn * TL::WTN + sl * 8;
-        if (row >= M || col >= N) continue;
-        const u16x8 v = *reinterpret_cast<const u16x8*>(ctile + rr * ROWB + ((sl ^ (rr & (SLOTS - 1))) << 4));
-        unsigned short* dst = Y + (int64_t)row * ldy + col;
-        if (col + 8 <= N && (((uintptr_t)dst) & 15) == 0) {
-            *reinterpret_cast<u16x8*>(dst) = v;
-        } else {
-            for (int u = 0; u < 8 && col + u < N; ++u) dst[u] = v[u];
-        }
-    }
-}
-
-// Epilogue shared by the 256x256 kernels: + bias[n] + scale * T[row,:] . B_k[n,:], bf16 via a
-// per-wave LDS staging tile (16-B slots XOR-swizzled by row), 16-B stores.
+// The VALU epilogue of k_lora_gemm and of k_lora_gemm8's MF = false path: + bias[n] + scale *
+// T[row,:] . B_k[n,:], bf16 via a per-wave LDS staging tile (WTM rows of WTN*2 bytes, 16-B slots
+// XOR-swizzled by row), 16-B stores.  The LoRA term is added row by row so accumulators retire as
+// they are written.  BMtile: rows of the workgroup tile (one member's B_k serves it unless it straddles).
 template <int R, int WTM, int WTN>
 __device__ __forceinline__ void lora_epilogue(f32x4 (&acc)[WTM / 16][WTN / 16], char* smem, int wave, int lane,
                                               int m0, int n0, int rbase, int cbase, const unsigned short* __restrict__ bias,
@@ -568,6 +386,60 @@ __device__ __forceinline__ void lora_epilogue(f32x4 (&acc)[WTM / 16][WTN / 16], 
             for (int u = 0; u < 8 && col + u < N; ++u) dst[u] = v[u];
         }
     }
+}
+
+template <int R>
+__global__ __launch_bounds__(T128::THREADS, 2) void k_lora_gemm(
+    const unsigned short* __restrict__ X, int64_t ldx, const unsigned short* __restrict__ W, int64_t ldw,
+    const unsigned short* __restrict__ bias, const float* __restrict__ T, const float* __restrict__ theta_pop,
+    int64_t ld_theta, int64_t offB, float scale, int rows_per_member, int M, int N, int64_t K, int tiles_n,
+    unsigned short* __restrict__ Y, int64_t ldy) {
+    using TL = T128;
+    constexpr int FM = TL::FM, FN = TL::FN;
+    __shared__ __attribute__((aligned(16))) char smem[TL::LDS];
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int wm = wave / TL::WN, wn = wave % TL::WN;
+    const TileIdx ti = p8_tile_index<TL::BM>(M, tiles_n);
+    const int m0 = ti.m * TL::BM, n0 = ti.n * TL::BN;
+
+    f32x4 acc[FM][FN];
+#pragma unroll
+    for (int i = 0; i < FM; ++i)
+#pragma unroll
+        for (int j = 0; j < FN; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+    const int nk = (int)(K / BK);
+    stage_rows<TL::GA>(X, ldx, m0, M - 1, 0, smem, wave, lane);
+    stage_rows<TL::GB>(W, ldw, n0, N - 1, 0, smem + TL::A_BYTES, wave, lane);
+    __syncthreads();
+    for (int kt = 0; kt < nk; ++kt) {
+        const char* cur = smem + (kt & 1) * TL::STAGE;
+        if (kt + 1 < nk) {
+            char* nxt = smem + ((kt + 1) & 1) * TL::STAGE;
+            stage_rows<TL::GA>(X, ldx, m0, M - 1, (int64_t)(kt + 1) * BK, nxt, wave, lane);
+            stage_rows<TL::GB>(W, ldw, n0, N - 1, (int64_t)(kt + 1) * BK, nxt + TL::A_BYTES, wave, lane);
+        }
+#pragma unroll
+        for (int kk = 0; kk < 2; ++kk) {
+            const int ch = kk * 4 + (lane >> 4);
+            bf16x8 b[FN];
+#pragma unroll
+            for (int f = 0; f < FN; ++f) b[f] = read_frag(cur + TL::A_BYTES, wn * TL::WTN + f * 16 + (lane & 15), ch);
+            bf16x8 a[FM];
+#pragma unroll
+            for (int f = 0; f < FM; ++f) a[f] = read_frag(cur, wm * TL::WTM + f * 16 + (lane & 15), ch);
+            __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+            for (int i = 0; i < FM; ++i)
+#pragma unroll
+                for (int j = 0; j < FN; ++j)
+                    acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[i], b[j], acc[i][j], 0, 0, 0);
+            __builtin_amdgcn_s_setprio(0);
+        }
+        __syncthreads();
+    }
+    lora_epilogue<R, TL::WTM, TL::WTN>(acc, smem, wave, lane, m0, n0, wm * TL::WTM, wn * TL::WTN, bias, T, theta_pop,
+                                       ld_theta, offB, scale, rows_per_member, TL::BM, M, N, Y, ldy);
 }
 
 // Epilogue operands of the MFMA LoRA addend, prefetched into LDS (after the 128 KiB ring) by
@@ -1014,52 +886,41 @@ __global__ __launch_bounds__(256) void k_lora_delta_f32(const float* __restrict_
     }
 }
 
-template <int R, int NI>
-static void launch_project_ra(const void* X, int64_t ldx, const float* tp, int64_t ldt, int64_t offA, int64_t rpm,
-                              int64_t M, int64_t K, float* T, hipStream_t st) {
-    const int64_t rows_per_block = 4 * PR_ROWS;
-    hipLaunchKernelGGL((k_lora_project_ra<R, NI>), dim3((unsigned)((M + rows_per_block - 1) / rows_per_block)),
-                       dim3(256), 0, st, (const unsigned short*)X, ldx, tp, ldt, offA, rpm, M, K, T);
-}
+// The instantiated kernels (dispatch_int, common.h).
+using RanksAll = std::integer_sequence<int, 0, 1, 2, 3, 4, 8, 16>;
+using RanksMF = std::integer_sequence<int, 0, 1, 2>;  // the MFMA-addend path
+using RanksProject = std::integer_sequence<int, 1, 2, 3, 4, 8, 16>;
+using ProjectNI = std::integer_sequence<int, 1, 2, 3, 4, 5, 6, 8>;  // k_lora_project_ra: 512-column steps of K
+using ProjectNQ = std::integer_sequence<int, 1, 2, 3, 4, 5, 6, 7, 8>;  // k_lora_project_mfma: n_lin * r
+using RanksDelta = std::integer_sequence<int, 1, 2, 3, 4, 5, 6, 7, 8>;
 
-template <int R>
-static void launch_project(const void* X, int64_t ldx, const float* tp, int64_t ldt, int64_t offA, int64_t rpm,
-                           int64_t M, int64_t K, float* T, hipStream_t st) {
-    if constexpr (R <= 2) {  // register-resident A for K <= 4096
-        const int64_t ni = (K + 511) / 512;
-        switch (ni) {
-            case 1: return launch_project_ra<R, 1>(X, ldx, tp, ldt, offA, rpm, M, K, T, st);
-            case 2: return launch_project_ra<R, 2>(X, ldx, tp, ldt, offA, rpm, M, K, T, st);
-            case 3: return launch_project_ra<R, 3>(X, ldx, tp, ldt, offA, rpm, M, K, T, st);
-            case 4: return launch_project_ra<R, 4>(X, ldx, tp, ldt, offA, rpm, M, K, T, st);
-            case 5: return launch_project_ra<R, 5>(X, ldx, tp, ldt, offA, rpm, M, K, T, st);
-            case 6: return launch_project_ra<R, 6>(X, ldx, tp, ldt, offA, rpm, M, K, T, st);
-            case 8: return launch_project_ra<R, 8>(X, ldx, tp, ldt, offA, rpm, M, K, T, st);
-            default: break;
-        }
-    }
-    hipLaunchKernelGGL(k_lora_project<R>, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, st,
-                       (const unsigned short*)X, ldx, tp, ldt, offA, rpm, M, K, T);
-}
-
+// T = X A_k^T: the register-resident-A kernel for r <= 2 where ceil(K / 512) is one of ProjectNI's step
+// counts (K <= 4096, 7 steps excepted), else k_lora_project.
 static int project(const void* X, int64_t ldx, const float* tp, int64_t ldt, int64_t offA, int32_t r, int64_t rpm,
                    int64_t M, int64_t K, float* T, hipStream_t st) {
-    switch (r) {
-        case 1: launch_project<1>(X, ldx, tp, ldt, offA, rpm, M, K, T, st); break;
-        case 2: launch_project<2>(X, ldx, tp, ldt, offA, rpm, M, K, T, st); break;
-        case 3: launch_project<3>(X, ldx, tp, ldt, offA, rpm, M, K, T, st); break;
-        case 4: launch_project<4>(X, ldx, tp, ldt, offA, rpm, M, K, T, st); break;
-        case 8: launch_project<8>(X, ldx, tp, ldt, offA, rpm, M, K, T, st); break;
-        case 16: launch_project<16>(X, ldx, tp, ldt, offA, rpm, M, K, T, st); break;
-        default: set_error("lora: r=%d unsupported (1,2,3,4,8,16)", r); return EGGROLL_ERR_UNSUPPORTED;
+    const unsigned short* x = (const unsigned short*)X;
+    const bool ok = dispatch_int(r, RanksProject{}, [&](auto Rc) {
+        constexpr int R = decltype(Rc)::value;
+        if constexpr (R <= 2) {
+            const int64_t rows_per_block = 4 * PR_ROWS;
+            const int64_t ni = (K + 511) / 512;
+            if (ni <= 8 && dispatch_int((int)ni, ProjectNI{}, [&](auto NI) {
+                    hipLaunchKernelGGL((k_lora_project_ra<R, decltype(NI)::value>),
+                                       dim3((unsigned)((M + rows_per_block - 1) / rows_per_block)), dim3(256), 0, st, x,
+                                       ldx, tp, ldt, offA, rpm, M, K, T);
+                }))
+                return;
+        }
+        hipLaunchKernelGGL(k_lora_project<R>, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, st, x, ldx, tp, ldt, offA,
+                           rpm, M, K, T);
+    });
+    if (!ok) {
+        set_error("lora: r=%d unsupported (1,2,3,4,8,16)", r);
+        return EGGROLL_ERR_UNSUPPORTED;
     }
     EGG_CHECK_LAUNCH("lora_project");
     return EGGROLL_OK;
 }
-
-// The instantiated kernels (dispatch_int, common.h).
-using RanksAll = std::integer_sequence<int, 0, 1, 2, 3, 4, 8, 16>;
-using RanksMF = std::integer_sequence<int, 0, 1, 2>;  // the MFMA-addend path
 using EpiOps = std::integer_sequence<int, EPI_NONE, EPI_SILU, EPI_RES, EPI_GATED, EPI_RES32, EPI_GATED32, EPI_GELU,
                                      EPI_MUL, EPI_GELU_ERF>;
 
@@ -1091,13 +952,12 @@ static int unsupported_r(int32_t r) {
     return EGGROLL_ERR_UNSUPPORTED;
 }
 
-// One-barrier tiles (kernels 128 / 256).
-template <class TL>
+// The one-barrier tile (kernel 128).
 static int launch_gemm(const GemmArgs& g, hipStream_t st) {
-    const int64_t tiles_m = (g.M + TL::BM - 1) / TL::BM, tiles_n = (g.N + TL::BN - 1) / TL::BN;
+    const int64_t tiles_m = (g.M + T128::BM - 1) / T128::BM, tiles_n = (g.N + T128::BN - 1) / T128::BN;
     EGG_CHECK_ARG(tiles_m * tiles_n < (1ll << 31), "lora_gemm: grid too large");
     if (!dispatch_int(g.r, RanksAll{}, [&](auto R) {
-            launch_tiles(k_lora_gemm<decltype(R)::value, TL>, tiles_m, tiles_n, TL::THREADS, g, st);
+            launch_tiles(k_lora_gemm<decltype(R)::value>, tiles_m, tiles_n, T128::THREADS, g, st);
         }))
         return unsupported_r(g.r);
     EGG_CHECK_LAUNCH("lora_gemm");
@@ -1152,13 +1012,67 @@ static int launch_gemm8(const GemmArgs& g, bool mf, int32_t epi, const EpiArgs& 
 
 // The operand checks every GEMM entry point shares, reported under the caller's name.  dma32: the
 // 8-phase kernels address X and W through 32-bit buffer offsets.
-static int gemm_args_ok(const char* api, int64_t ldx, int64_t ldw, int64_t ldy, int64_t rows_per_member, int64_t M,
-                        int64_t N, int64_t K, bool dma32) {
-    EGG_CHECK_ARG(ldx % 8 == 0 && ldw % 8 == 0 && ldx >= K && ldw >= K && ldy >= N, "%s: bad strides", api);
-    EGG_CHECK_ARG(M < (1ll << 31) && N < (1ll << 31) && rows_per_member < (1ll << 31), "%s: M/N too large", api);
-    EGG_CHECK_ARG(!dma32 || M == 0 || (M * ldx * 2 < (1ll << 31) && N * ldw * 2 < (1ll << 31)), "%s: operand > 2 GiB",
+static int gemm_args_ok(const char* api, const GemmArgs& g, bool dma32) {
+    EGG_CHECK_ARG(g.ldx % 8 == 0 && g.ldw % 8 == 0 && g.ldx >= g.K && g.ldw >= g.K && g.ldy >= g.N, "%s: bad strides",
                   api);
+    EGG_CHECK_ARG(g.M < (1ll << 31) && g.N < (1ll << 31) && g.rows_per_member < (1ll << 31), "%s: M/N too large", api);
+    EGG_CHECK_ARG(!dma32 || g.M == 0 || (g.M * g.ldx * 2 < (1ll << 31) && g.N * g.ldw * 2 < (1ll << 31)),
+                  "%s: operand > 2 GiB", api);
     return EGGROLL_OK;
+}
+
+// Kernel choice is a per-call argument (no process-global state: the C-ABI is thread-safe per
+// stream).  0 = automatic: an 8-phase kernel (gemm8_auto) when the grid still fills the chip, else the
+// 128x128 one-barrier tile.  8 / 9 = 8-phase 256x256 with MFMA / VALU LoRA epilogue, 10 = 8-phase
+// 256x320, 128 = the one-barrier tile.
+// Every argument check of the plain GEMM entry points, reported under the caller's name, before
+// anything is launched; *tsel: the kernel that will run.
+static int plain_args_ok(const char* api, const GemmArgs& g, int32_t kernel, int* tsel) {
+    EGG_CHECK_ARG(kernel == 0 || kernel == 8 || kernel == 9 || kernel == 10 || kernel == 128,
+                  "%s: kernel must be 0 (auto), 8, 9, 10 or 128 (got %d)", api, kernel);
+    EGG_CHECK_ARG(g.M >= 0 && g.N > 0 && g.K > 0, "%s: bad sizes M=%lld N=%lld K=%lld", api, (long long)g.M,
+                  (long long)g.N, (long long)g.K);
+    EGG_CHECK_ARG(g.K % 64 == 0, "%s: K=%lld must be a multiple of 64", api, (long long)g.K);
+    EGG_CHECK_ARG(g.r >= 0 && g.r <= 16, "%s: r=%d out of range", api, g.r);
+    EGG_CHECK_ARG(g.rows_per_member > 0, "%s: rows_per_member must be > 0", api);
+    *tsel = kernel ? kernel
+                   : ((g.M / 256) * ((g.N + 255) / 256) >= 512 ? gemm8_auto(g.M, g.N, g.r, g.rows_per_member, EPI_NONE)
+                                                               : 128);
+    return gemm_args_ok(api, g, *tsel != 128);
+}
+
+// The plain GEMM on kernel tsel, arguments checked by plain_args_ok (M > 0).
+static int lora_gemm_launch(const char* api, int tsel, const GemmArgs& g, hipStream_t st) {
+    EGG_CHECK_ARG(g.X && g.W && g.Y, "%s: NULL pointer", api);
+    EGG_CHECK_ARG(g.r == 0 || (g.T && g.theta_pop), "%s: T / theta_pop NULL with r > 0", api);
+    if (tsel == 128) return launch_gemm(g, st);
+    if (tsel == 10 && gemm8n_ok(g.r, g.rows_per_member))  // else: kernel 8's VALU-epilogue path, as kernel 8 does
+        return launch_gemm8<G8<2, 5>>(g, true, EPI_NONE, EpiArgs{}, st);
+    return launch_gemm8<G8<2>>(g, tsel != 9 && g.r <= 2 && g.rows_per_member >= 256, EPI_NONE, EpiArgs{}, st);
+}
+
+// The epilogue checks of the _epi_ entry points (epi != EPI_NONE), in plain_args_ok's manner.
+static int epi_args_ok(const char* api, const GemmArgs& g, int32_t epi, const EpiArgs& ea, int32_t kernel) {
+    EGG_CHECK_ARG(kernel == 0 || kernel == 8 || kernel == 10, "%s: kernel must be 0, 8 or 10", api);
+    EGG_CHECK_ARG(epi >= EPI_SILU && epi <= EPI_GELU_ERF, "%s: epi=%d unknown", api, epi);
+    EGG_CHECK_ARG(g.r >= 0 && g.r <= 2, "%s: r=%d (epilogue ops need r <= 2)", api, g.r);
+    EGG_CHECK_ARG(g.r == 0 || g.rows_per_member >= 256, "%s: rows_per_member must be >= 256 with r > 0", api);
+    EGG_CHECK_ARG(g.M >= 0 && g.N > 0 && g.K > 0 && g.K % 64 == 0, "%s: need K %% 64 == 0", api);
+    if (const int rc = gemm_args_ok(api, g, true)) return rc;
+    EGG_CHECK_ARG(epi == EPI_SILU || epi == EPI_GELU || epi == EPI_GELU_ERF || (ea.res && ea.ldr >= g.N),
+                  "%s: res NULL or ldr < N", api);
+    EGG_CHECK_ARG((epi != EPI_GATED && epi != EPI_GATED32) || (ea.gate && ea.gstride >= g.N && ea.rpg > 0),
+                  "%s: bad gate", api);
+    if (g.M == 0) return EGGROLL_OK;
+    EGG_CHECK_ARG(g.X && g.W && (g.Y || epi == EPI_RES32 || epi == EPI_GATED32), "%s: NULL pointer", api);
+    return EGGROLL_OK;
+}
+
+// The epilogue GEMM with T = X A_k^T already computed, arguments checked by epi_args_ok (M > 0).
+static int gemm_epi_impl(GemmArgs g, int32_t epi, const EpiArgs& ea, int32_t kernel, hipStream_t st) {
+    if (g.r == 0) g.rows_per_member = g.M;  // no members without a LoRA term: the addend sees one
+    if (kernel == 0) kernel = gemm8_auto(g.M, g.N, g.r, g.rows_per_member, epi);
+    return kernel == 10 ? launch_gemm8<G8<2, 5>>(g, true, epi, ea, st) : launch_gemm8<G8<2>>(g, true, epi, ea, st);
 }
 
 
@@ -1208,17 +1122,11 @@ int eggroll_lora_project_multi(const void* X, int64_t ldx, const float* theta_po
     const unsigned grid = (unsigned)((M + PM_ROWS_PER_BLOCK - 1) / PM_ROWS_PER_BLOCK);
     const size_t lds = (size_t)K * 32;
     hipStream_t st = as_stream(stream);
-#define EGG_PM_CASE(nq)                                                                                          \
-    case nq:                                                                                                     \
-        hipLaunchKernelGGL(k_lora_project_mfma<nq>, dim3(grid), dim3(256), lds, st, (const unsigned short*)X, ldx, \
-                           theta_pop, ld_theta, off[0], off[1], off[2], off[3], (int)r, rows_per_member, M, K, T); \
-        break;
-    switch (n_lin * r) {
-        EGG_PM_CASE(1) EGG_PM_CASE(2) EGG_PM_CASE(3) EGG_PM_CASE(4)
-        EGG_PM_CASE(5) EGG_PM_CASE(6) EGG_PM_CASE(7) EGG_PM_CASE(8)
-        default: break;
-    }
-#undef EGG_PM_CASE
+    dispatch_int(n_lin * r, ProjectNQ{}, [&](auto NQ) {  // 1 <= n_lin * r <= 8: checked above
+        hipLaunchKernelGGL(k_lora_project_mfma<decltype(NQ)::value>, dim3(grid), dim3(256), lds, st,
+                           (const unsigned short*)X, ldx, theta_pop, ld_theta, off[0], off[1], off[2], off[3], (int)r,
+                           rows_per_member, M, K, T);
+    });
     EGG_CHECK_LAUNCH("lora_project_multi");
     return EGGROLL_OK;
 }
@@ -1247,80 +1155,30 @@ int eggroll_lora_delta_f32(const float* x, int64_t ldx, const float* A, int64_t 
     EGG_CHECK_ARG(x && A && B && y, "lora_delta_f32: NULL pointer");
     const int64_t blocks = std::min<int64_t>((M + 3) / 4, 2048);
     hipStream_t st = as_stream(stream);
-#define EGG_DELTA(RV)                                                                                            \
-    case RV:                                                                                                     \
-        hipLaunchKernelGGL(k_lora_delta_f32<RV>, dim3((unsigned)blocks), dim3(256), 0, st, x, ldx, A, lda_member, \
-                           B, ldb_member, scale, rows_per_member, M, (int)N, (int)K, y, ldy);                    \
-        break;
-    switch (r) {
-        EGG_DELTA(1) EGG_DELTA(2) EGG_DELTA(3) EGG_DELTA(4) EGG_DELTA(5) EGG_DELTA(6) EGG_DELTA(7) EGG_DELTA(8)
-    }
-#undef EGG_DELTA
+    dispatch_int(r, RanksDelta{}, [&](auto R) {  // 1 <= r <= 8: checked above
+        hipLaunchKernelGGL(k_lora_delta_f32<decltype(R)::value>, dim3((unsigned)blocks), dim3(256), 0, st, x, ldx, A,
+                           lda_member, B, ldb_member, scale, rows_per_member, M, (int)N, (int)K, y, ldy);
+    });
     EGG_CHECK_LAUNCH("lora_delta_f32");
     return EGGROLL_OK;
-}
-
-// Kernel choice is a per-call argument (no process-global state: the C-ABI is thread-safe per
-// stream).  0 = automatic: the 8-phase 256x256 kernel when the grid still fills the chip, else the
-// 128x128 one-barrier tile.  8 / 9 = 8-phase 256x256 with MFMA / VALU LoRA epilogue, 10 = 8-phase
-// 256x320, 128 / 256 = one-barrier tiles.
-// Every argument check of the plain GEMM entry points, reported under the caller's name, before
-// anything is launched; *tsel: the kernel that will run.
-static int plain_args_ok(const char* api, int64_t ldx, int64_t ldw, int64_t ldy, int32_t r, int64_t rows_per_member,
-                         int64_t M, int64_t N, int64_t K, int32_t kernel, int* tsel) {
-    EGG_CHECK_ARG(kernel == 0 || kernel == 8 || kernel == 9 || kernel == 10 || kernel == 128 || kernel == 256,
-                  "%s: kernel must be 0 (auto), 8, 9, 10, 128 or 256 (got %d)", api, kernel);
-    EGG_CHECK_ARG(M >= 0 && N > 0 && K > 0, "%s: bad sizes M=%lld N=%lld K=%lld", api, (long long)M, (long long)N,
-                  (long long)K);
-    EGG_CHECK_ARG(K % 64 == 0, "%s: K=%lld must be a multiple of 64", api, (long long)K);
-    EGG_CHECK_ARG(r >= 0 && r <= 16, "%s: r=%d out of range", api, r);
-    EGG_CHECK_ARG(rows_per_member > 0, "%s: rows_per_member must be > 0", api);
-    *tsel = kernel ? kernel
-                   : ((M / 256) * ((N + 255) / 256) >= 512 ? gemm8_auto(M, N, r, rows_per_member, EPI_NONE) : 128);
-    const bool p8 = *tsel == 8 || *tsel == 9 || *tsel == 10;
-    return gemm_args_ok(api, ldx, ldw, ldy, rows_per_member, M, N, K, p8);
-}
-
-// The plain GEMM on kernel tsel, arguments checked by plain_args_ok (M > 0).
-static int lora_gemm_launch(const char* api, int tsel, const void* X, int64_t ldx, const void* W, int64_t ldw,
-                            const void* bias, const float* T, const float* theta_pop, int64_t ld_theta, int64_t offB,
-                            int32_t r, float scale, int64_t rows_per_member, int64_t M, int64_t N, int64_t K, void* Y,
-                            int64_t ldy, void* stream) {
-    EGG_CHECK_ARG(X && W && Y, "%s: NULL pointer", api);
-    EGG_CHECK_ARG(r == 0 || (T && theta_pop), "%s: T / theta_pop NULL with r > 0", api);
-    hipStream_t st = as_stream(stream);
-    const GemmArgs g{X, ldx, W, ldw, bias, T, theta_pop, ld_theta, offB, r, scale, rows_per_member, M, N, K, Y, ldy};
-    if (tsel == 10 && gemm8n_ok(r, rows_per_member))  // else: kernel 8's VALU-epilogue path, as kernel 8 does
-        return launch_gemm8<G8<2, 5>>(g, true, EPI_NONE, EpiArgs{}, st);
-    if (tsel == 8 || tsel == 9 || tsel == 10)
-        return launch_gemm8<G8<2>>(g, tsel != 9 && r <= 2 && rows_per_member >= 256, EPI_NONE, EpiArgs{}, st);
-    return tsel == 256 ? launch_gemm<kT256>(g, st) : launch_gemm<kT128>(g, st);
-}
-
-static int lora_gemm_impl(const void* X, int64_t ldx, const void* W, int64_t ldw, const void* bias, const float* T,
-                          const float* theta_pop, int64_t ld_theta, int64_t offB, int32_t r, float scale,
-                          int64_t rows_per_member, int64_t M, int64_t N, int64_t K, void* Y, int64_t ldy,
-                          int32_t kernel, void* stream) {
-    int tsel;
-    if (const int rc = plain_args_ok("lora_gemm", ldx, ldw, ldy, r, rows_per_member, M, N, K, kernel, &tsel)) return rc;
-    if (M == 0) return EGGROLL_OK;
-    return lora_gemm_launch("lora_gemm", tsel, X, ldx, W, ldw, bias, T, theta_pop, ld_theta, offB, r, scale,
-                            rows_per_member, M, N, K, Y, ldy, stream);
-}
-
-int eggroll_lora_gemm(const void* X, int64_t ldx, const void* W, int64_t ldw, const void* bias, const float* T,
-                      const float* theta_pop, int64_t ld_theta, int64_t offB, int32_t r, float scale,
-                      int64_t rows_per_member, int64_t M, int64_t N, int64_t K, void* Y, int64_t ldy, void* stream) {
-    return lora_gemm_impl(X, ldx, W, ldw, bias, T, theta_pop, ld_theta, offB, r, scale, rows_per_member, M, N, K, Y,
-                          ldy, 0, stream);
 }
 
 int eggroll_lora_gemm_sel(const void* X, int64_t ldx, const void* W, int64_t ldw, const void* bias, const float* T,
                           const float* theta_pop, int64_t ld_theta, int64_t offB, int32_t r, float scale,
                           int64_t rows_per_member, int64_t M, int64_t N, int64_t K, void* Y, int64_t ldy,
                           int32_t kernel, void* stream) {
-    return lora_gemm_impl(X, ldx, W, ldw, bias, T, theta_pop, ld_theta, offB, r, scale, rows_per_member, M, N, K, Y,
-                          ldy, kernel, stream);
+    const GemmArgs g{X, ldx, W, ldw, bias, T, theta_pop, ld_theta, offB, r, scale, rows_per_member, M, N, K, Y, ldy};
+    int tsel;
+    if (const int rc = plain_args_ok("lora_gemm", g, kernel, &tsel)) return rc;
+    if (M == 0) return EGGROLL_OK;
+    return lora_gemm_launch("lora_gemm", tsel, g, as_stream(stream));
+}
+
+int eggroll_lora_gemm(const void* X, int64_t ldx, const void* W, int64_t ldw, const void* bias, const float* T,
+                      const float* theta_pop, int64_t ld_theta, int64_t offB, int32_t r, float scale,
+                      int64_t rows_per_member, int64_t M, int64_t N, int64_t K, void* Y, int64_t ldy, void* stream) {
+    return eggroll_lora_gemm_sel(X, ldx, W, ldw, bias, T, theta_pop, ld_theta, offB, r, scale, rows_per_member, M, N, K,
+                                 Y, ldy, 0, stream);
 }
 
 int64_t eggroll_lora_workspace_bytes(int64_t M, int64_t K, int32_t r, int64_t rows_per_member) {
@@ -1333,10 +1191,10 @@ int eggroll_lora_linear_pop_sel(const void* X, int64_t ldx, const void* W, int64
                                 const float* theta_pop, int64_t ld_theta, int64_t offA, int64_t offB, int32_t r,
                                 float scale, int64_t rows_per_member, int64_t M, int64_t N, int64_t K, void* Y,
                                 int64_t ldy, float* T_ws, int32_t kernel, void* stream) {
+    const GemmArgs g{X, ldx, W, ldw, bias, T_ws, theta_pop, ld_theta, offB, r, scale, rows_per_member, M, N, K, Y, ldy};
     // every check of the GEMM before the projection is launched: a refused call launches nothing
     int tsel;
-    if (const int rc = plain_args_ok("lora_linear_pop", ldx, ldw, ldy, r, rows_per_member, M, N, K, kernel, &tsel))
-        return rc;
+    if (const int rc = plain_args_ok("lora_linear_pop", g, kernel, &tsel)) return rc;
     if (M == 0) return EGGROLL_OK;
     EGG_CHECK_ARG(X && W && Y, "lora_linear_pop: NULL pointer");
     EGG_CHECK_ARG(r == 0 || (theta_pop && T_ws), "lora_linear_pop: theta_pop / T_ws NULL with r > 0");
@@ -1344,41 +1202,7 @@ int eggroll_lora_linear_pop_sel(const void* X, int64_t ldx, const void* W, int64
         int rc = eggroll_lora_project(X, ldx, theta_pop, ld_theta, offA, r, rows_per_member, M, K, T_ws, stream);
         if (rc) return rc;
     }
-    return lora_gemm_launch("lora_linear_pop", tsel, X, ldx, W, ldw, bias, T_ws, theta_pop, ld_theta, offB, r, scale,
-                            rows_per_member, M, N, K, Y, ldy, stream);
-}
-
-// The epilogue GEMM with T = X A_k^T already computed (shared by linear_pop_epi and lora_gemm_epi).
-static int gemm_epi_impl(const void* X, int64_t ldx, const void* W, int64_t ldw, const void* bias, const float* T,
-                         const float* theta_pop, int64_t ld_theta, int64_t offB, int32_t r, float scale,
-                         int64_t rows_per_member, int64_t M, int64_t N, int64_t K, void* Y, int64_t ldy, int32_t epi,
-                         const void* res, int64_t ldr, const void* gate, int64_t gstride, int64_t rows_per_group,
-                         int32_t kernel, void* stream) {
-    const EpiArgs ea{(const unsigned short*)res, ldr, (const unsigned short*)gate, gstride, rows_per_group};
-    const int64_t rpm = r ? rows_per_member : (M > 0 ? M : 1);
-    if (kernel == 0) kernel = gemm8_auto(M, N, r, rpm, epi);
-    const GemmArgs g{X, ldx, W, ldw, bias, T, theta_pop, ld_theta, offB, r, scale, rpm, M, N, K, Y, ldy};
-    return kernel == 10 ? launch_gemm8<G8<2, 5>>(g, true, epi, ea, as_stream(stream))
-                        : launch_gemm8<G8<2>>(g, true, epi, ea, as_stream(stream));
-}
-
-static int epi_args_ok(const char* api, const void* X, int64_t ldx, const void* W, int64_t ldw, int32_t r,
-                       int64_t rows_per_member, int64_t M, int64_t N, int64_t K, const void* Y, int64_t ldy,
-                       int32_t epi, const void* res, int64_t ldr, const void* gate, int64_t gstride,
-                       int64_t rows_per_group, int32_t kernel) {
-    EGG_CHECK_ARG(kernel == 0 || kernel == 8 || kernel == 10, "%s: kernel must be 0, 8 or 10", api);
-    EGG_CHECK_ARG(epi >= EPI_SILU && epi <= EPI_GELU_ERF, "%s: epi=%d unknown", api, epi);
-    EGG_CHECK_ARG(r >= 0 && r <= 2, "%s: r=%d (epilogue ops need r <= 2)", api, r);
-    EGG_CHECK_ARG(r == 0 || rows_per_member >= 256, "%s: rows_per_member must be >= 256 with r > 0", api);
-    EGG_CHECK_ARG(M >= 0 && N > 0 && K > 0 && K % 64 == 0, "%s: need K %% 64 == 0", api);
-    if (const int rc = gemm_args_ok(api, ldx, ldw, ldy, rows_per_member, M, N, K, true)) return rc;
-    EGG_CHECK_ARG(epi == EPI_SILU || epi == EPI_GELU || epi == EPI_GELU_ERF || (res && ldr >= N),
-                  "%s: res NULL or ldr < N", api);
-    EGG_CHECK_ARG((epi != EPI_GATED && epi != EPI_GATED32) || (gate && gstride >= N && rows_per_group > 0),
-                  "%s: bad gate", api);
-    if (M == 0) return EGGROLL_OK;
-    EGG_CHECK_ARG(X && W && (Y || epi == EPI_RES32 || epi == EPI_GATED32), "%s: NULL pointer", api);
-    return EGGROLL_OK;
+    return lora_gemm_launch("lora_linear_pop", tsel, g, as_stream(stream));
 }
 
 int eggroll_lora_linear_pop_epi_sel(const void* X, int64_t ldx, const void* W, int64_t ldw, const void* bias,
@@ -1392,16 +1216,16 @@ int eggroll_lora_linear_pop_epi_sel(const void* X, int64_t ldx, const void* W, i
         return eggroll_lora_linear_pop_sel(X, ldx, W, ldw, bias, theta_pop, ld_theta, offA, offB, r, scale,
                                            rows_per_member, M, N, K, Y, ldy, T_ws, kernel, stream);
     }
-    const int rc0 = epi_args_ok("lora_linear_pop_epi", X, ldx, W, ldw, r, rows_per_member, M, N, K, Y, ldy, epi, res,
-                                ldr, gate, gstride, rows_per_group, kernel);
+    const GemmArgs g{X, ldx, W, ldw, bias, T_ws, theta_pop, ld_theta, offB, r, scale, rows_per_member, M, N, K, Y, ldy};
+    const EpiArgs ea{(const unsigned short*)res, ldr, (const unsigned short*)gate, gstride, rows_per_group};
+    const int rc0 = epi_args_ok("lora_linear_pop_epi", g, epi, ea, kernel);
     if (rc0 || M == 0) return rc0;
     if (r > 0) {
         EGG_CHECK_ARG(theta_pop && T_ws, "lora_linear_pop_epi: theta_pop / T_ws NULL with r > 0");
         int rc = eggroll_lora_project(X, ldx, theta_pop, ld_theta, offA, r, rows_per_member, M, K, T_ws, stream);
         if (rc) return rc;
     }
-    return gemm_epi_impl(X, ldx, W, ldw, bias, T_ws, theta_pop, ld_theta, offB, r, scale, rows_per_member, M, N, K, Y,
-                         ldy, epi, res, ldr, gate, gstride, rows_per_group, kernel, stream);
+    return gemm_epi_impl(g, epi, ea, kernel, as_stream(stream));
 }
 
 int eggroll_lora_gemm_epi_sel(const void* X, int64_t ldx, const void* W, int64_t ldw, const void* bias, const float* T,
@@ -1409,12 +1233,12 @@ int eggroll_lora_gemm_epi_sel(const void* X, int64_t ldx, const void* W, int64_t
                               int64_t rows_per_member, int64_t M, int64_t N, int64_t K, void* Y, int64_t ldy,
                               int32_t epi, const void* res, int64_t ldr, const void* gate, int64_t gstride,
                               int64_t rows_per_group, int32_t kernel, void* stream) {
-    const int rc0 = epi_args_ok("lora_gemm_epi", X, ldx, W, ldw, r, rows_per_member, M, N, K, Y, ldy, epi, res, ldr,
-                                gate, gstride, rows_per_group, kernel);
+    const GemmArgs g{X, ldx, W, ldw, bias, T, theta_pop, ld_theta, offB, r, scale, rows_per_member, M, N, K, Y, ldy};
+    const EpiArgs ea{(const unsigned short*)res, ldr, (const unsigned short*)gate, gstride, rows_per_group};
+    const int rc0 = epi_args_ok("lora_gemm_epi", g, epi, ea, kernel);
     if (rc0 || M == 0) return rc0;
     EGG_CHECK_ARG(r == 0 || (T && theta_pop), "lora_gemm_epi: T / theta_pop NULL with r > 0");
-    return gemm_epi_impl(X, ldx, W, ldw, bias, T, theta_pop, ld_theta, offB, r, scale, rows_per_member, M, N, K, Y, ldy,
-                         epi, res, ldr, gate, gstride, rows_per_group, kernel, stream);
+    return gemm_epi_impl(g, epi, ea, kernel, as_stream(stream));
 }
 
 int eggroll_lora_linear_pop_epi(const void* X, int64_t ldx, const void* W, int64_t ldw, const void* bias,

@@ -268,7 +268,7 @@ def fitness(S: torch.Tensor, promptnorm: bool, eps: float = 1e-8) -> Dict[str, t
 class UpdateWorkspace:
     def __init__(self, layout: ThetaLayout, device):
         nbytes = int(_lib.load().eggroll_update_workspace_bytes(layout.n_tiles))
-        self.buf = torch.zeros(-(-nbytes // 16) * 16, dtype=torch.uint8, device=device)  # done counter starts at 0
+        self.buf = torch.zeros(-(-nbytes // 16) * 16, dtype=torch.uint8, device=device)  # per-tile fp64 norm partials + the caps' scalars
 
 
 def update(theta: torch.Tensor, factors: torch.Tensor, fit: Dict[str, torch.Tensor], layout: ThetaLayout, pop: int,
@@ -323,7 +323,7 @@ def lora_linear_pop(x: torch.Tensor, W: torch.Tensor, bias: Optional[torch.Tenso
     x: [M, K] bf16; W: [N, K] bf16; bias: [N] bf16 or None; theta_pop: [n_members, ld] fp32.
     r = 0 runs the plain base GEMM (no LoRA term).  kernel: 0 = automatic choice, else an explicit
     kernel for A/B measurement (eggroll_lora_linear_pop_sel): 8 / 9 the 256x256 8-phase kernel with the
-    MFMA / VALU LoRA epilogue, 10 the 256x320 8-phase kernel, 128 / 256 the one-barrier tiles."""
+    MFMA / VALU LoRA epilogue, 10 the 256x320 8-phase kernel, 128 the 128x128 one-barrier tile."""
     _dev(x, "lora_linear_pop(x)", torch.bfloat16)
     _dev(W, "lora_linear_pop(W)", torch.bfloat16)
     M, K = x.shape
@@ -437,7 +437,7 @@ def lora_gemm(x: torch.Tensor, W: torch.Tensor, bias: Optional[torch.Tensor], T:
               theta_pop: Optional[torch.Tensor], offB: int, r: int, scale: float, rows_per_member: int,
               out: Optional[torch.Tensor] = None, kernel: int = 0) -> torch.Tensor:
     """The MFMA GEMM + fused LoRA epilogue alone, given T = X A_k^T (from lora_project).
-    kernel: 0 automatic, 8 / 9 / 10 / 128 / 256 as lora_linear_pop (eggroll_lora_gemm_sel)."""
+    kernel: 0 automatic, 8 / 9 / 10 / 128 as lora_linear_pop (eggroll_lora_gemm_sel)."""
     _dev(x, "lora_gemm(x)", torch.bfloat16)
     _dev(W, "lora_gemm(W)", torch.bfloat16)
     M, K = x.shape
@@ -455,8 +455,8 @@ def lora_gemm(x: torch.Tensor, W: torch.Tensor, bias: Optional[torch.Tensor], T:
 def gemm_tile_for(M: int, N: int, r: int = 2, rows_per_member: int = 1 << 30, epi: Optional[str] = None) -> int:
     """Kernel libeggroll's automatic choice uses for an M x N LoRA GEMM (mirrors plain_args_ok / gemm_epi_impl
     / gemm8_auto): 8 = the 8-phase 256x256 kernel, 10 = the 8-phase 256x320 kernel, 128 = the 128x128
-    one-barrier tile (no epilogue op only).  It never returns 9 (kernel 8's tile with the VALU epilogue) or
-    256 (the 256x256 one-barrier tile), the other ids the selectors accept."""
+    one-barrier tile (no epilogue op only).  It never returns 9 (kernel 8's tile with the VALU epilogue),
+    the other id the selectors accept."""
     if epi is None and (M // 256) * ((N + 255) // 256) < 512:
         return 128
     if not (r == 0 or (r <= 2 and rows_per_member >= 256)) or epi in ("res", "gated", "mul"):

@@ -221,7 +221,7 @@ int eggroll_lora_gemm(const void* X, int64_t ldx, const void* W, int64_t ldw, co
  * measurement: 0 = automatic (as above: the 8-phase 256x256 kernel when the grid fills the chip,
  * else 128x128); 8 = 8-phase with the MFMA LoRA epilogue, 9 = 8-phase with a VALU epilogue,
  * 10 = 8-phase 256x320 tile with the MFMA LoRA epilogue (r <= 2 with rows_per_member >= 256, or
- * r = 0; bit-identical to 8), 128 / 256 = one-barrier tiles.  Any other id (0, 8, 9, 10, 128, 256
+ * r = 0; bit-identical to 8), 128 = the 128x128 one-barrier tile.  Any other id (0, 8, 9, 10, 128
  * are all there are) is refused with EGGROLL_ERR_ARG before anything is launched.                   */
 int eggroll_lora_gemm_sel(const void* X, int64_t ldx, const void* W, int64_t ldw, const void* bias,
                           const float* T, const float* theta_pop, int64_t ld_theta, int64_t offB,

@@ -49,11 +49,19 @@ def test_argument_errors_are_reported():
     rc = lib.eggroll_lora_gemm_sel(None, 64, None, 64, None, None, None, 0, 0, 2, 1.0, 10, 10, 10, 64, None, 10, 12,
                                    None)  # kernel 12 (the removed fused-projection kernel) is not a kernel id
     assert rc == -1 and lib.eggroll_last_error().startswith(b"lora_gemm: ")
-    assert b"0 (auto), 8, 9, 10, 128 or 256 (got 12)" in lib.eggroll_last_error()
+    assert b"0 (auto), 8, 9, 10 or 128 (got 12)" in lib.eggroll_last_error()
     rc = lib.eggroll_lora_linear_pop_sel(None, 64, None, 64, None, None, 0, 0, 0, 2, 1.0, 10, 10, 10, 64, None, 10,
                                          None, 12, None)
     assert rc == -1 and lib.eggroll_last_error().startswith(b"lora_linear_pop: ")
     assert lib.eggroll_last_error().endswith(b"(got 12)")
+    rc = lib.eggroll_lora_gemm_sel(None, 64, None, 64, None, None, None, 0, 0, 2, 1.0, 10, 10, 10, 64, None, 10, 256,
+                                   None)  # kernel 256 (the removed 256x256 one-barrier tile) is not a kernel id
+    assert rc == -1 and lib.eggroll_last_error().startswith(b"lora_gemm: ")
+    assert b"0 (auto), 8, 9, 10 or 128 (got 256)" in lib.eggroll_last_error()
+    rc = lib.eggroll_lora_linear_pop_sel(None, 64, None, 64, None, None, 0, 0, 0, 2, 1.0, 10, 10, 10, 64, None, 10,
+                                         None, 256, None)
+    assert rc == -1 and lib.eggroll_last_error().startswith(b"lora_linear_pop: ")
+    assert lib.eggroll_last_error().endswith(b"(got 256)")
     with pytest.raises(_lib.EggrollError):
         _lib.check(-1, "probe")
 

@@ -12,7 +12,8 @@ Layouts:  L0 packed (strides = sizes, allocator bases: what the rest of the suit
 Shapes:   S1 = 600 x 203 x 128, 260 rows per member: three 256-row tiles (the last ragged), members changing
           inside tiles, two K-tiles, N = 25 * 8 + 3 (a 3-column element tail; odd, so packed rows alternate
           between aligned and unaligned);  S2 = 300 x 331 x 192, 100 rows per member: three K-tiles, two
-          column tiles for 256- and 320-wide tiles, members shorter than a tile (r 3 / 4, tiles 128 / 256 / 9)."""
+          column tiles for 256- and 320-wide tiles, members shorter than a tile (r 3 / 4, tiles 128 / 9 and the
+          automatic choice, tile 0)."""
 import functools
 import re
 
@@ -165,9 +166,9 @@ def _run(c, layout, api, kernel, epi=None, inplace=False, y_null=False):
 
 # ---------------------------------------------------------------------------------- 1. plain GEMM, every tile kind
 PLAIN = ([(t, "S1", r) for t in (8, 10) for r in (0, 1, 2)] +
-         [(t, "S1", r) for t in (128, 256, 9) for r in (0, 2)] +
-         [(t, "S2", r) for t in (128, 256, 9) for r in (3, 4)] +
-         [(t, "S2", 0) for t in (128, 256, 8, 9, 10)])
+         [(t, "S1", r) for t in (128, 0, 9) for r in (0, 2)] +
+         [(t, "S2", r) for t in (128, 0, 9) for r in (3, 4)] +
+         [(t, "S2", 0) for t in (128, 0, 8, 9, 10)])
 PLAIN = [(t, s, r, api) for t, s, r in PLAIN for api in ("linear_pop", "gemm")]
 
 
@@ -175,7 +176,9 @@ PLAIN = [(t, s, r, api) for t, s, r in PLAIN for api in ("linear_pop", "gemm")]
 def test_plain_gemm_layouts(dev, tile, shape, r, api):
     """Every tile kind, through eggroll_lora_linear_pop_sel and eggroll_lora_gemm_sel: the packed call is
     within the suite's bf16 bound of the fp64 oracle; the padded-aligned and padded-unaligned calls equal it
-    bit for bit (no arithmetic depends on a stride); nothing outside [M, N] is written or read."""
+    bit for bit (no arithmetic depends on a stride); nothing outside [M, N] is written or read.  Tile 0 is the
+    library's automatic choice: its packed output equals, bit for bit, that of the kernel kernels.gemm_tile_for
+    names (the Python mirror agrees with the library)."""
     c = _case(shape, r)
     y = {L: _run(c, L, api, tile)["y"] for L in LAYOUTS}
     got = y["L0"].view(torch.bfloat16).float().cpu().numpy()
@@ -183,6 +186,9 @@ def test_plain_gemm_layouts(dev, tile, shape, r, api):
     assert (err <= lora_tol(c["ref"], c["Kd"])).all(), float(err.max())
     for L in ("L1", "L2"):
         assert torch.equal(y[L], y["L0"]), f"{L} differs from L0 in {int((y[L] != y['L0']).sum())} elements"
+    if tile == 0:
+        named = K.gemm_tile_for(c["M"], c["N"], r, c["rpm"])
+        assert torch.equal(y["L0"], _run(c, "L0", api, named)["y"]), f"automatic choice differs from kernel {named}"
 
 
 # ---------------------------------------------------------------------------------- 2. every epilogue op
@@ -356,6 +362,7 @@ REFUSED = [
     ("K=96", PLAIN_EP + EPI_EP, "silu", dict(K=96, ldx=96, ldw=96)),
     ("kernel=7", PLAIN_EP + EPI_EP, "silu", dict(kernel=7)),
     ("kernel=12", PLAIN_EP + EPI_EP, "silu", dict(kernel=12)),     # the removed fused-projection kernel
+    ("kernel=256", PLAIN_EP + EPI_EP, "silu", dict(kernel=256)),   # the removed 256x256 one-barrier tile
     ("kernel=9-epi", EPI_EP, "silu", dict(kernel=9)),
     ("r=3-epi", EPI_EP, "silu", dict(r=3)),
     ("r=2-rpm=255-epi", EPI_EP, "silu", dict(rpm=255)),

@@ -275,8 +275,8 @@ def _bf(x):
     return x.to(torch.bfloat16)
 
 
-@pytest.fixture(params=[128, 256, 8, 9, 10],
-                ids=["tile128", "tile256", "tile8phase_mfma", "tile8phase_valu", "tile8phase_320"])
+@pytest.fixture(params=[128, 0, 8, 9, 10],
+                ids=["tile128", "auto", "tile8phase_mfma", "tile8phase_valu", "tile8phase_320"])
 def gemm_tile(request):
     return request.param
 

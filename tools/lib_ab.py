@@ -4,9 +4,11 @@ every library bound by ctypes in one process, seeded inputs, HIP events on the l
     python tools/lib_ab.py build-a [REV]               build a committed revision's library into
                                                        tools/_stamps/libeggroll_a.so
     python tools/lib_ab.py A.so B.so [KERNEL]          bitwise equality on ragged / member-straddling / bias / no-bias
-                                                       cases, then interleaved timing at the Sana-1.6B shapes
+                                                       cases, then interleaved timing at the Sana-1.6B shapes (r 2) and
+                                                       at 8192 x 2240 x 2240, which the automatic choice gives to
+                                                       kernel 128 (r 0 / 2 / 16); "spread" = the largest |1 - A/B|
     python tools/lib_ab.py bits A.so B.so              bitwise equality at the shapes of tests/test_gpu_gemm_layouts.py,
-                                                       kernels 0 / 8 / 9 / 10 / 128 / 256, r 0 / 1 / 2 / 4, both entry points
+                                                       kernels 0 / 8 / 9 / 10 / 128, r 0 / 1 / 2 / 4, both entry points
 """
 import ctypes
 import json
@@ -119,16 +121,19 @@ def main(pa, pb, kern=8):
         assert same
 
     res = {}
-    for M, N, K in ((131072, 2240, 2240), (131072, 11200, 2240), (131072, 2240, 5632)):
-        c = Case(libs, M, N, K, 16384, 2, True)
-        med = c.time((0, 1), kern)
+    timed = [(131072, 2240, 2240, 16384, 2), (131072, 11200, 2240, 16384, 2), (131072, 2240, 5632, 16384, 2)]
+    timed += [(8192, 2240, 2240, 2048, r) for r in (0, 2, 16)]
+    for M, N, K, rpm, r in timed:
+        c = Case(libs, M, N, K, rpm, r, True)
+        med = c.time((0, 1), kern, reps=5 if M > 8192 else 50)   # a timed window of several ms either way
         a, b = med[0], med[1]
         tf = 2 * M * N * K / 1e9
-        res[f"{M}x{N}x{K}"] = {"A_ms": round(a, 4), "B_ms": round(b, 4), "A_TF": round(tf / a, 1),
-                               "B_TF": round(tf / b, 1), "B_vs_A": round(a / b, 4),
-                               "bitwise_equal": torch.equal(c.ys[0], c.ys[1])}
-        print(json.dumps({f"{M}x{N}x{K}": res[f"{M}x{N}x{K}"]}), flush=True)
+        key = f"{M}x{N}x{K}-r{r}"
+        res[key] = {"A_ms": round(a, 4), "B_ms": round(b, 4), "A_TF": round(tf / a, 1), "B_TF": round(tf / b, 1),
+                    "B_vs_A": round(a / b, 4), "bitwise_equal": torch.equal(c.ys[0], c.ys[1])}
+        print(json.dumps({key: res[key]}), flush=True)
         del c
+    res["spread"] = round(max(abs(1 - v["A_ms"] / v["B_ms"]) for v in res.values()), 4)
     print(json.dumps(res))
 
 
@@ -138,7 +143,7 @@ def bits(pa, pb):
     for M, N, K, rpm in ((600, 203, 128, 260), (300, 331, 192, 100)):   # S1, S2 of tests/test_gpu_gemm_layouts.py
         for r in (0, 1, 2, 4):
             c = Case(libs, M, N, K, rpm, r, True)
-            for kern in (0, 8, 9, 10, 128, 256):
+            for kern in (0, 8, 9, 10, 128):
                 for api in ("gemm", "linear_pop"):
                     same = c.equal(kern, api)
                     n += 1
